@@ -12,8 +12,12 @@ before the timed region.
 Run: ``python bench.py [--gpus N --steps K --warmup W]``.  For N > 1 the driver uses
 ``torch.distributed.run`` and each rank reads RANK/LOCAL_RANK/WORLD_SIZE; without a
 launcher ``--gpus N`` starts the N rank processes itself (``launch_ranks``).
-Rank 0 prints one JSON line (roofline of the fused interaction kernel measured
-with HIP events over the timed region; CPU baseline = the oracle restatement).
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints
+the line (roofline of the fused interaction kernel from the HIP events of the timed region).
+``--full`` adds what takes runs of its own: the in-line steps behind the roofline figure
+(``--inline-steps``) and the CPU baseline (the oracle restatement; ``--no-cpu-baseline``
+leaves it out).  ``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy`` (``dump_outputs``), for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -298,6 +302,41 @@ def cpu_baseline_cgc(modified: bool, p, n_nodes: int, n_edges: int, budget_s: fl
                       f"edges, 3 warm-up + median of {len(times)} step(s) ({med * 1e3:.1f} ms/step)"}
 
 
+DUMP_BUDGET_BYTES = 64 * 2**20   # --dump-outputs: cap on all the files together
+
+
+def dump_outputs(outdir: str, arrays: dict) -> dict:
+    """``--dump-outputs``: write each tensor as ``outdir/<name>.npy`` (float32, or float64 where
+    the tensor is), at most DUMP_BUDGET_BYTES in all.  An array over its equal share of the budget
+    is stored as a fixed sample of its flattened entries (sorted indices from a generator seeded
+    with 0, the same from run to run).  Returns {name: {"shape", "stored", "sampled"}}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        cap = share // a.itemsize
+        sampled = a.size > cap
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": list(t.shape), "stored": int(a.size), "sampled": bool(sampled)}
+    return info
+
+
+def step_outputs(pred, loss, plist) -> dict:
+    """What a caller of the timed step holds after it: the model's prediction and the loss of that
+    step, the gradients it left on the parameters (after all-reduce and clipping, where the step
+    has them) and the parameters after the optimizer update, each flattened in parameter order."""
+    zero = lambda p: torch.zeros_like(p)  # noqa: E731  (a parameter the loss does not reach)
+    return {"stiffness": pred, "loss": loss.reshape(1),
+            "grads": torch.cat([(p.grad if p.grad is not None else zero(p)).reshape(-1) for p in plist]),
+            "params": torch.cat([p.detach().reshape(-1) for p in plist])}
+
+
 def main_cgc(args):
     """BASELINE config 4: CGC / mCGC (scripts/train_cgcnn_*.py) on the same synthetic lattices.
     One step = forward + loss + backward + flat all-reduce + AdamW (hidden 128 / 64, 3 passes)."""
@@ -326,11 +365,12 @@ def main_cgc(args):
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = stiffness_loss(model(batch)["stiffness"], target)
+        pred = model(batch)["stiffness"]
+        loss = stiffness_loss(pred, target)
         loss.backward()
         allreduce()
         opt.step()
-        return loss
+        return loss, pred
 
     for _ in range(args.warmup):
         step()
@@ -341,7 +381,7 @@ def main_cgc(args):
     ops.TIMER.records.clear()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, pred = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -383,7 +423,9 @@ def main_cgc(args):
                           "global_batch": args.batch * world, "parallelism": f"graph-sharded dp{world}"},
                "backend": backend, "rehearsal": backend == "gloo",
                "loss": round(float(loss.item()), 6), "roofline": roof, "cpu_baseline": None}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, step_outputs(pred, loss, list(model.parameters())))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_cgc(modified, p, args.nodes, args.edges, min(args.cpu_budget, 10.0))
         if args.kernel_summary:
             print(json.dumps(ksum, indent=1), file=sys.stderr)
@@ -404,7 +446,13 @@ def main():
     ap.add_argument("--lmax", type=int, default=4)
     ap.add_argument("--correlation", type=int, default=3, choices=[1, 2, 3, 4],
                     help="symmetric-contraction correlation (4: the table-driven kernels, lmax <= 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the in-line steps behind "
+                         "the roofline figure (--inline-steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (prediction, loss, "
+                         "gradients, updated parameters) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=25.0)
     ap.add_argument("--cpu-full", action="store_true",
                     help="(default) CPU baseline with BASELINE.md section 2's 3 warm-up + 10 timed steps")
@@ -412,8 +460,8 @@ def main():
                     help="CPU baseline with 1 warm-up + timed steps within --cpu-budget (at least 1)")
     ap.add_argument("--kernel-summary", action="store_true", help="print per-kernel timings to stderr")
     ap.add_argument("--inline-steps", type=int, default=5,
-                    help="in-line steps after the timed region whose tp_fwd launch time gives the "
-                         "roofline (0: the overlapped timed region's own figure)")
+                    help="--full: in-line steps after the timed region whose tp_fwd launch time gives "
+                         "the roofline (0, or without --full: the overlapped timed region's own figure)")
     ap.add_argument("--model", default="egnn", choices=["egnn", "cgc_modified", "cgc_vanilla"],
                     help="egnn = the headline EnergyEquivGNN; cgc_* = BASELINE config 4 benchmark models")
     ap.add_argument("--optimizer", default="fused", choices=["fused", "foreach"],
@@ -479,12 +527,13 @@ def main():
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = stiffness_loss(model(batch)["stiffness"], batch.stiffness)
+        pred = model(batch)["stiffness"]
+        loss = stiffness_loss(pred, batch.stiffness)
         loss.backward()
         allreduce()                      # one flat fp32 RCCL all-reduce (no-op at N=1)
         torch.nn.utils.clip_grad_norm_(plist, 10.0)
         opt.step()
-        return loss
+        return loss, pred
 
     for _ in range(args.warmup):
         step()
@@ -495,7 +544,7 @@ def main():
     ops.TIMER.records.clear()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, pred = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -507,11 +556,15 @@ def main():
         dt = float(t.item())
     ksum = ops.TIMER.summary()
     same = params_equal_across_ranks(plist) if (world > 1 and args.check_params) else None
-    # the roofline kernel's launch time in the in-line step (every kernel on the main stream,
-    # EELG_OVERLAP=0's order), after the timed region: the figure a rocprofv3 kernel trace of
-    # this command reproduces (profiles/r08a_frac_probe.md); the overlapped timed region's own
-    # HIP-event figure is reported beside it
-    ksum_inl = inline_kernel_times(step, args.inline_steps) if args.inline_steps > 0 else {}
+    # before anything else steps the model: rank 0's arrays of the last timed step
+    dumped = (dump_outputs(args.dump_outputs, step_outputs(pred, loss, plist))
+              if (args.dump_outputs and rank == 0) else None)
+    # --full: the roofline kernel's launch time in the in-line step (every kernel on the main
+    # stream, EELG_OVERLAP=0's order), after the timed region: the figure a rocprofv3 kernel trace
+    # of this command reproduces (profiles/r08a_frac_probe.md); the overlapped timed region's own
+    # HIP-event figure is reported beside it, and is the roofline figure of a plain run
+    ksum_inl = (inline_kernel_times(step, args.inline_steps)
+                if (args.full and args.inline_steps > 0) else {})
 
     if rank == 0:
         n_tot = args.batch * args.nodes
@@ -548,7 +601,7 @@ def main():
                 # in-edge, not once per node, so > 1 is expected for a gather)
                 roof["traffic_detail"]["ratio_to_algorithmic"] = round(roof["traffic"] / byts, 3)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.nodes, args.edges, args.layers, args.cpu_budget, args.lmax,
                                full=not args.cpu_quick, correlation=args.correlation)
         value = world * args.batch * args.steps / dt
@@ -580,6 +633,8 @@ def main():
         }
         if same is not None:
             out["params_equal_across_ranks"] = same
+        if dumped is not None:
+            out["outputs"] = dumped
         if args.kernel_summary:
             print(json.dumps(ksum, indent=1), file=sys.stderr)
         print(json.dumps(out), flush=True)

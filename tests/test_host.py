@@ -368,3 +368,32 @@ def test_bench_traffic_lookup_finds_every_workloads_roofline_kernel():
     for args, kernel in cases:
         t = bench.pmc_traffic(kernel, args)
         assert t is not None and t["bytes"] > 1e9, (bench.workload_key(args), kernel)
+
+
+def test_bench_dump_outputs_is_capped_repeatable_and_float(tmp_path):
+    """bench.py --dump-outputs: every array lands as ``<name>.npy`` in float32 (float64 where the
+    tensor is), all files together stay under the 64 MB budget, an array over its share is a
+    fixed seeded sample (the same entries from run to run), a small one is stored whole."""
+    import importlib.util
+    import os
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_BUDGET_BYTES = 4096          # 3 arrays: 1365 B each = 341 float32 / 170 float64
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    arrays = {"small": torch.arange(6, dtype=torch.bfloat16), "big": big, "dbl": big.double()}
+    infos = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert infos[0] == infos[1]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert got["small"].dtype == np.float32 and got["big"].dtype == np.float32
+    assert got["dbl"].dtype == np.float64
+    assert np.array_equal(got["small"], np.arange(6, dtype=np.float32))
+    assert not infos[0]["small"]["sampled"] and infos[0]["big"]["sampled"]
+    assert got["big"].shape == (341,) and got["dbl"].shape == (170,)
+    # the sample: distinct entries of the array in index order (values == indices here)
+    assert np.all(np.diff(got["big"]) > 0) and set(got["big"]) <= set(range(1000))
+    assert sum(a.nbytes for a in got.values()) <= 4096
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

@@ -10,7 +10,7 @@ O=$R/gpurun_out/$1; shift; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 run() { local log=$1 t=$2; shift 2; timeout -k 10 "$t" "$@" > "$O/$log" 2>&1; local rc=$?
         echo "[$log] rc=$rc $(tail -1 "$O/$log" | cut -c1-160)"; [ $rc -eq 0 ] || exit $rc; }
-B="$R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --kernel-summary"
+B="$R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --kernel-summary"
 modes=${*:-ovl inl_rf inl_old}
 for m in $modes; do
   case $m in

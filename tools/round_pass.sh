@@ -7,7 +7,7 @@
 #   tests                 the whole `pytest -m gpu` suite (EELG_PARITY_OUT -> parity.json)
 #   pytest:<files>[:<k>]  pytest -m gpu over <files> ('+' between files), -k <k> ('+' for spaces)
 #   smoke                 __graft_entry__.smoke()
-#   bench[:<args>]        bench.py line (args with '+' for spaces, e.g. bench:--config+5)
+#   bench[:<args>]        bench.py --full line (args with '+' for spaces, e.g. bench:--config+5)
 #   prof:<name>[:<args>]  tools/profile_round.sh for a workload (bench args as above)
 #   inline                EELG_OVERLAP=0 rocprofv3 kernel trace of the default bench command
 #   kbench[:<regex>]      tools/kbench.py --reps 20 [--only regex]
@@ -36,13 +36,13 @@ for s in "$@"; do
                if [ -n "$k" ]; then step "t_$n.log" 600 env EELG_PARITY_OUT="$O/parity_$n.json" $PYT -m gpu $f -k "$k"
                else step "t_$n.log" 600 env EELG_PARITY_OUT="$O/parity_$n.json" $PYT -m gpu $f; fi ;;
     smoke)     step smoke.log 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)     step bench.json 400 python3 bench.py ;;
+    bench)     step bench.json 400 python3 bench.py --full ;;
     bench:*)   a=$(sp "${s#bench:}"); n=$(echo "${s#bench:}" | tr -c 'a-zA-Z0-9_' '_' | cut -c1-40)
-               step "bench_$n.json" 400 python3 bench.py $a ;;
+               step "bench_$n.json" 400 python3 bench.py --full $a ;;
     prof:*)    r=${s#prof:}; n=${r%%:*}; a=""; [ "$r" != "$n" ] && a=$(sp "${r#*:}")
                step "prof_$n.log" 900 env BENCH_ARGS="$a" bash tools/profile_round.sh "gpurun_out/$TAG/$n" ;;
     inline)    step inline.log 300 env EELG_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv \
-                   -d "$O/inline" -o run -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline ;;
+                   -d "$O/inline" -o run -- python3 "$R/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline ;;
     kbench)    step kbench.txt 300 python3 "$R/tools/kbench.py" --reps 20 ;;
     kbench:*)  step "kbench_$(echo "${s#kbench:}" | tr -c 'a-zA-Z0-9_' '_' | cut -c1-30).txt" 300 \
                    python3 "$R/tools/kbench.py" --reps 20 --only "${s#kbench:}" ;;

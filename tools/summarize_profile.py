@@ -70,8 +70,8 @@ def main(src, tag, wk=DEFAULT_WK):
     byts = b["roofline"]["bytes_per_launch"]
     lines = [f"# Profile {tag}", "",
              f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps "
-             f"{tb['steps'] if tb else 5} --warmup {tb['warmup'] if tb else 2} --no-cpu-baseline` "
-             f"({steps_traced} traced steps); bench line from `python3 bench.py --steps "
+             f"{tb['steps'] if tb else 5} --warmup {tb['warmup'] if tb else 2} --full --no-cpu-baseline` "
+             f"({steps_traced} traced steps); bench line from `python3 bench.py --full --steps "
              f"{b['steps']} --warmup {b['warmup']}` on the same box.", "",
              f"bench: **{b['value']} {b['unit']}**, {b['ms_per_step']} ms/step; roofline kernel "
              f"{b['roofline']['kernel']}: {b['roofline']['mean_ms']} ms/launch (HIP events), "
