@@ -175,13 +175,10 @@ template <int CTRL>
 __device__ __forceinline__ float eelg_dpp_f(float x) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
 }
-__device__ __forceinline__ void eelg_lane_reduce64(float* v) {
-#pragma unroll
-  for (int i = 0; i < 32; ++i) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 32]),
-                                                    false, false);
-    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
+// The same over each half-wave on its own, 32 slots: afterwards lane L holds, in v[0], the sum
+// over the 32 lanes of its half-wave of slot L & 31 (the steps on the lane bits 16, 8, 4, 2, 1;
+// none of them crosses the half-wave boundary).  Fixed order.
+__device__ __forceinline__ void eelg_lane_reduce32(float* v) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 16]),
@@ -218,4 +215,13 @@ __device__ __forceinline__ void eelg_lane_reduce64(float* v) {
     const float keep = up ? v[1] : v[0], give = up ? v[0] : v[1];
     v[0] = keep + eelg_dpp_f<0xB1>(give);      // quad_perm [1,0,3,2] = lane ^ 1
   }
+}
+__device__ __forceinline__ void eelg_lane_reduce64(float* v) {
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 32]),
+                                                    false, false);
+    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  }
+  eelg_lane_reduce32(v);   // the remaining 32 slots over the lane bits 16 .. 1
 }

@@ -889,6 +889,73 @@ __global__ __launch_bounds__(256) void radial_bwd_wo_kernel(const void* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
+// backward 4: grad of the MLP input (the edge features; geometry gradients only)
+// ---------------------------------------------------------------------------------------------
+// From grad_h (radial_bwd_gh_kernel) and the saved pre-activations, for n = NH-1 .. 0:
+//   gz_n = grad_h_n * SiLU'(z_n);  grad_h_{n-1} = gz_n W_n;  grad_feats = gz_0 W_0   [E, n_feat].
+// Every weight sits in LDS.  A wave owns RBX_EB consecutive edges (grid-stride); lane c is hidden
+// column c (feature c in the last product): it writes its gz into the wave's LDS tile [column][edge]
+// and forms its column of gz W by walking the rows j of W in order -- one W read and two
+// broadcast float4 reads of the tile per j for RBX_EB FMAs.  Plain fp32 FMAs in a fixed order.
+#define RBX_EB 8
+template <int H, int NH>
+__global__ __launch_bounds__(256) void radial_bwd_x_kernel(const float* __restrict__ ghin, int n_edges,
+                                                           eelg_radial_desc d,
+                                                           const float* __restrict__ zsave,
+                                                           float* __restrict__ gfeats) {
+  constexpr int NHM = NH > 1 ? NH - 1 : 1;
+  __shared__ float WS[NHM * H * H];   // W_1 .. W_{NH-1}, [out j][in c]
+  __shared__ float W0[H * 32];        // W_0 [H][n_feat]
+  __shared__ __attribute__((aligned(16))) float GZ[4][H * RBX_EB];
+  const int wave = threadIdx.x >> 6, c = threadIdx.x & 63;
+  const int nf = d.n_feat;
+#pragma unroll
+  for (int n = 1; n < NH; ++n)
+    for (int t = threadIdx.x; t < H * H; t += 256) WS[(n - 1) * H * H + t] = d.w[n][t];
+  for (int t = threadIdx.x; t < H * nf; t += 256) W0[t] = d.w[0][t];
+  __syncthreads();
+  float* __restrict__ gzw = GZ[wave];
+  const bool col = c < H;
+  const int ngrp = (n_edges + RBX_EB - 1) / RBX_EB;
+  for (int t = blockIdx.x * 4 + wave; t < ngrp; t += gridDim.x * 4) {
+    const int e0 = t * RBX_EB;
+    float gh[RBX_EB];
+#pragma unroll
+    for (int b = 0; b < RBX_EB; ++b)
+      gh[b] = rad_ld(ghin, (size_t)(e0 + b) * H + c, col && e0 + b < n_edges);
+#pragma unroll
+    for (int n = NH - 1; n >= 0; --n) {
+#pragma unroll
+      for (int b = 0; b < RBX_EB; ++b) {
+        const float z = rad_ld(zsave, ((size_t)n * n_edges + e0 + b) * H + c, col && e0 + b < n_edges);
+        if (col) gzw[c * RBX_EB + b] = rad_silu_grad(z, gh[b]);
+      }
+      __builtin_amdgcn_wave_barrier();
+      const float* __restrict__ wn = n > 0 ? WS + (n - 1) * H * H : W0;
+      const int ld = n > 0 ? H : nf;
+      const bool on = n > 0 ? col : c < nf;
+#pragma unroll
+      for (int b = 0; b < RBX_EB; ++b) gh[b] = 0.0f;
+#pragma unroll 4   // (fully unrolled at H = 32 the loop took 256 VGPRs, one wave per SIMD)
+      for (int j = 0; j < H; ++j) {
+        const float wv = on ? wn[j * ld + c] : 0.0f;
+        const float4 g0 = *reinterpret_cast<const float4*>(gzw + j * RBX_EB);
+        const float4 g1 = *reinterpret_cast<const float4*>(gzw + j * RBX_EB + 4);
+        gh[0] = fmaf(g0.x, wv, gh[0]); gh[1] = fmaf(g0.y, wv, gh[1]);
+        gh[2] = fmaf(g0.z, wv, gh[2]); gh[3] = fmaf(g0.w, wv, gh[3]);
+        gh[4] = fmaf(g1.x, wv, gh[4]); gh[5] = fmaf(g1.y, wv, gh[5]);
+        gh[6] = fmaf(g1.z, wv, gh[6]); gh[7] = fmaf(g1.w, wv, gh[7]);
+      }
+      __builtin_amdgcn_wave_barrier();   // the tile is rewritten by the next layer / edge group
+    }
+    if (c < nf)
+#pragma unroll
+      for (int b = 0; b < RBX_EB; ++b)
+        if (e0 + b < n_edges) gfeats[(size_t)(e0 + b) * nf + c] = gh[b];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
 // the exact three-part bf16 split of an fp32 array (eelg_split_bf16x3): parts[p * n + i]
@@ -988,6 +1055,21 @@ int eelg_split_bf16x3(const float* src, long long n, void* parts, void* stream) 
 
 static bool rad_a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// backward 1 (grad_h = grad_w W_o) of every radial backward entry: hidden 32 / 64, fp32 / bf16 grad_w
+static int rad_launch_gh(const void* grad_w, bool bf, int n_edges, const eelg_radial_desc* d,
+                         const unsigned short* wotp, float* grad_h, hipStream_t st) {
+  const dim3 g1((n_edges + 127) / 128);
+  const int W = d->n_out;
+  if (d->hidden == 64) {
+    if (bf) hipLaunchKernelGGL((radial_bwd_gh_kernel<64, true>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
+    else hipLaunchKernelGGL((radial_bwd_gh_kernel<64, false>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
+  } else {
+    if (bf) hipLaunchKernelGGL((radial_bwd_gh_kernel<32, true>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
+    else hipLaunchKernelGGL((radial_bwd_gh_kernel<32, false>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
+  }
+  return eelg_check_launch("radial_bwd_gh");
+}
+
 int eelg_radial_fwd(const float* feats, int n_edges, const eelg_radial_desc* d, const void* wo_parts,
                     int out_bf16, float* zsave, void* out, void* stream) {
   if (int rc = radial_check(d, n_edges, out_bf16 ? 2 : 4)) return rc;
@@ -1014,11 +1096,8 @@ int eelg_radial_bwd_chain(const void* grad_w, int grad_bf16, int n_edges, const 
   const bool bf = grad_bf16 != 0;
   int nw, ns, tps;
   radial_plan(n_edges, d->n_out, &nw, &ns, &tps);
-  const dim3 g1((n_edges + 127) / 128);
   const int W = d->n_out;
-  if (bf) hipLaunchKernelGGL((radial_bwd_gh_kernel<64, true>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-  else hipLaunchKernelGGL((radial_bwd_gh_kernel<64, false>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-  if (int rc = eelg_check_launch("radial_bwd_gh")) return rc;
+  if (int rc = rad_launch_gh(grad_w, bf, n_edges, d, wotp, grad_h, st)) return rc;
   const int ntile = (n_edges + 31) / 32;
   const dim3 g2((unsigned)((ntile + 3) / 4 < 2048 ? (ntile + 3) / 4 : 2048));
   if (d->n_hidden == 1)
@@ -1033,6 +1112,31 @@ int eelg_radial_bwd_chain(const void* grad_w, int grad_bf16, int n_edges, const 
   return eelg_check_launch("radial_bwd_wo");
 }
 
+int eelg_radial_bwd_gh(const void* grad_w, int grad_bf16, int n_edges, const eelg_radial_desc* d,
+                       const void* wot_parts, float* grad_h, void* stream) {
+  if (int rc = radial_check(d, n_edges, grad_bf16 ? 2 : 4)) return rc;
+  if (!rad_a16(wot_parts) || !rad_a16(grad_w))
+    return eelg_fail(-2, "radial_bwd_gh: grad_w and wot_parts must be 16-byte aligned");
+  if (n_edges == 0) return 0;
+  const unsigned short* wotp = static_cast<const unsigned short*>(wot_parts);
+  return rad_launch_gh(grad_w, grad_bf16 != 0, n_edges, d, wotp, grad_h, (hipStream_t)stream);
+}
+
+int eelg_radial_bwd_x(const float* grad_h, int n_edges, const eelg_radial_desc* d,
+                      const float* zsave, float* grad_feats, void* stream) {
+  if (int rc = radial_check(d, n_edges, 4)) return rc;
+  if (n_edges == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int ngrp = (n_edges + RBX_EB - 1) / RBX_EB;
+  const dim3 grid((unsigned)((ngrp + 3) / 4 < 2048 ? (ngrp + 3) / 4 : 2048));
+#define RAD_BX(HH, NN) hipLaunchKernelGGL((radial_bwd_x_kernel<HH, NN>), grid, dim3(256), 0, st, grad_h, n_edges, *d, zsave, grad_feats)
+  const int h_ = d->hidden, nh_ = d->n_hidden;
+  if (h_ == 64) { if (nh_ == 1) RAD_BX(64, 1); else if (nh_ == 2) RAD_BX(64, 2); else RAD_BX(64, 3); }
+  else { if (nh_ == 1) RAD_BX(32, 1); else if (nh_ == 2) RAD_BX(32, 2); else RAD_BX(32, 3); }
+#undef RAD_BX
+  return eelg_check_launch("radial_bwd_x");
+}
+
 int eelg_radial_bwd(const void* grad_w, int grad_bf16, int n_edges, const eelg_radial_desc* d,
                     const void* wot_parts, const float* zsave, const float* feats, float* grad_h,
                     float* part_h, float* part_wo, void* stream) {
@@ -1045,16 +1149,8 @@ int eelg_radial_bwd(const void* grad_w, int grad_bf16, int n_edges, const eelg_r
   const bool bf = grad_bf16 != 0;
   int nw, ns, tps;
   radial_plan(n_edges, d->n_out, &nw, &ns, &tps);
-  const dim3 g1((n_edges + 127) / 128);
   const int W = d->n_out;
-  if (d->hidden == 64) {
-    if (bf) hipLaunchKernelGGL((radial_bwd_gh_kernel<64, true>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-    else hipLaunchKernelGGL((radial_bwd_gh_kernel<64, false>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-  } else {
-    if (bf) hipLaunchKernelGGL((radial_bwd_gh_kernel<32, true>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-    else hipLaunchKernelGGL((radial_bwd_gh_kernel<32, false>), g1, dim3(256), 0, st, grad_w, n_edges, W, wotp, grad_h);
-  }
-  if (int rc = eelg_check_launch("radial_bwd_gh")) return rc;
+  if (int rc = rad_launch_gh(grad_w, bf, n_edges, d, wotp, grad_h, st)) return rc;
   const dim3 g2(nw);
   const int h_ = d->hidden, nh_ = d->n_hidden;
 #define RAD_SMALL(HH, NN) hipLaunchKernelGGL((radial_bwd_small_kernel<HH, NN>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, feats, part_h)

@@ -236,6 +236,43 @@ def emit_sh(lmax: int) -> str:
     return "\n".join(L)
 
 
+def emit_sh_bwd(lmax: int) -> str:
+    """Gradient of ``sh_eval_l<lmax>`` w.r.t. the edge vector: the recursion
+    ``y_{l+1,k} = sum c_ijk y_{l,i} n_j`` run forward for the y's, then in reverse from lmax down
+    to 1 for the adjoint of the unit vector n, then ``(nbar - n (n . nbar)) / |v|``."""
+    L = []
+    L.append(f"// gradient of sh_eval_l{lmax} (g: the row's {(lmax + 1) ** 2} SH cotangents) w.r.t. (vx, vy, vz)")
+    L.append(f"__device__ __forceinline__ void sh_bwd_l{lmax}(float vx, float vy, float vz, const float* __restrict__ g, float* __restrict__ gv) {{")
+    L.append("  float n = sqrtf(vx * vx + vy * vy + vz * vz);")
+    L.append("  float inv = 1.0f / fmaxf(n, 1e-12f);")
+    L.append("  float v0 = vx * inv, v1 = vy * inv, v2 = vz * inv;")
+    L.append("  float y1_0 = v0, y1_1 = v1, y1_2 = v2;")
+    rec = cg.sh_recursion(lmax)
+    for l, terms in enumerate(rec, start=1):
+        if l + 1 == lmax:
+            break                      # y_lmax itself is not an operand of the reverse pass
+        acc: Dict[int, List[str]] = {}
+        for i, j, k, c in terms:
+            acc.setdefault(k, []).append(f"{flit(c)} * y{l}_{i} * v{j}")
+        for k in range(2 * l + 3):
+            L.append(f"  float y{l + 1}_{k} = {' + '.join(acc.get(k, ['0.0f']))};")
+    for l in range(1, lmax + 1):
+        s = math.sqrt(2 * l + 1)
+        for m in range(2 * l + 1):
+            L.append(f"  float b{l}_{m} = {flit(s)} * g[{l * l + m}];")
+    L.append("  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;")
+    for l in range(lmax - 1, 0, -1):
+        for i, j, k, c in rec[l - 1]:
+            L.append(f"  {{ const float t = {flit(c)} * b{l + 1}_{k}; b{l}_{i} = fmaf(t, v{j}, b{l}_{i}); "
+                     f"a{j} = fmaf(t, y{l}_{i}, a{j}); }}")
+    L.append("  a0 += b1_0; a1 += b1_1; a2 += b1_2;")
+    L.append("  // n = v / |v|: project out the radial part; at the 1e-12 clamp n = v * 1e12 is linear in v")
+    L.append("  const float dot = n > 1e-12f ? a0 * v0 + a1 * v1 + a2 * v2 : 0.0f;")
+    L.append("  gv[0] = (a0 - v0 * dot) * inv; gv[1] = (a1 - v1 * dot) * inv; gv[2] = (a2 - v2 * dot) * inv;")
+    L.append("}")
+    return "\n".join(L)
+
+
 # ---------------------------------------------------------------------------
 # tensor product
 # ---------------------------------------------------------------------------
@@ -1132,6 +1169,96 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
                 bwf=int(bwf), bwf_r=TP_BWF_R, tdim=target.dim,
                 sig=fnv1a64(tp_signature(node, sh, target)))
     return "\n".join(L), info
+
+
+def emit_tp_bwd_sh(name: str, node: Irreps, sh: Irreps, target: Irreps) -> Tuple[str, int]:
+    """``tp_bwd_sh_<name>``: the interaction's gradient w.r.t. the spherical harmonics,
+
+      grad_sh[e, l2^2 + j] = inv_norm sum_{p: l2} coef_p sum_u w[e,p,u] sum_{ik} C_p[i,j,k]
+                             x[sender(e), l1, u, i] grad_agg[receiver(e), p, u, k]
+
+    (the TP is linear in the SH, so they are not an operand).  One half-wave owns one edge for
+    every input block l1 and, at mul 64, both channel groups: lane u holds the (lmax+1)^2 partial
+    sums of its channel(s) in registers, the 32 lanes are then summed by ``eelg_lane_reduce32``
+    (fixed order), which leaves component q on lane q, and the padded row is written once by
+    lanes 0..nshp-1 (pad = sums of zeros).  At mul 16 lanes 16..31 contribute exact zeros.
+    The register figures (no scratch, tpB_l4_m64 140 VGPRs) depend on the
+    Makefile's -fno-slp-vectorize and on the channel-group loop staying rolled (unroll 1): without
+    the flag tpB_l4_m64 spills (256 VGPRs + 256 AGPRs, 596 B scratch).
+    Returns (code, nshp)."""
+    paths = cg.tp_paths(node, sh, target)
+    din, nsh = node.dim, sh.dim
+    nshp = (nsh + 3) // 4 * 4
+    assert nshp <= 32
+    dmid = cg.tp_out_irreps_with_instructions(node, sh, target)[0].dim
+    wn = sum(p.mul for p in paths)
+    node_ls = [ir.l for _, ir in node]
+    node_off = {ir.l: o for (m, ir), o in zip(node, node.offsets())}
+    bgroups = [[p for p in paths if p.l1 == l] for l in node_ls]
+    bgroups = [g for g in bgroups if g]
+    CG, LW = _chan_groups()
+    L: List[str] = []
+    L.append(f"// ===== SH gradient of tensor product config {name}: {len(paths)} paths, {nsh} components =====")
+    L.append(f"__global__ __launch_bounds__(256) void tp_bwd_sh_{name}(")
+    L.append("    const float* __restrict__ x, const float* __restrict__ w, const int* __restrict__ sender,")
+    L.append("    const int* __restrict__ receiver, int n_edges, const float* __restrict__ gagg,")
+    L.append("    float inv_norm, float* __restrict__ gsh) {")
+    L.append("  const int lane = threadIdx.x & 63, u = lane & 31;")
+    L.append("  // no early exit: the lane reduction below runs with every lane of the wave active; a")
+    L.append("  // half-wave past the last edge recomputes that edge and stores nothing")
+    L.append("  const int eq = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);")
+    L.append("  const bool live = eq < n_edges;")
+    L.append("  const int e = live ? eq : n_edges - 1;")
+    L.append(f"  const float* __restrict__ xs = x + (size_t)sender[e] * {din};")
+    L.append(f"  const float* __restrict__ ge = gagg + (size_t)receiver[e] * {dmid};")
+    L.append(f"  const float* __restrict__ we = w + (size_t)e * {wn};")
+    L.append("  float a[32];")
+    L.append("#pragma unroll")
+    L.append("  for (int q = 0; q < 32; ++q) a[q] = 0.0f;")
+    ind = "  "
+    if CG > 1:
+        L.append("#pragma unroll 1")
+        L.append(f"  for (int cgi = 0; cgi < {CG}; ++cgi) {{")
+        L.append("    const int uc = u + 32 * cgi;")
+        ind = "    "
+    elif LW < 32:
+        L.append(f"  const bool act = u < {LW};      // lanes without a channel read channel 0 and add zeros")
+        L.append("  const int uc = act ? u : 0;")
+    else:
+        L.append("  const int uc = u;")
+    for grp in bgroups:
+        l = grp[0].l1
+        d = 2 * l + 1
+        xs_ = [f"x{l}_{i}" for i in range(d)]
+        L.append(f"{ind}{{ // input block l1 = {l}")
+        L.append(f"{ind}  float " + ", ".join(xs_) + ";")
+        L += [f"{ind}  " + ln for ln in vec_load(xs_, "xs", f"{node_off[l]} + uc * {d}")]
+        for p in grp:
+            d3 = 2 * p.l3 + 1
+            gs_ = [f"g{k}" for k in range(d3)]
+            L.append(f"{ind}  {{ // slot {p.slot}: {p.l1} x {p.l2} -> {p.l3}")
+            L.append(f"{ind}    float " + ", ".join(gs_) + ";")
+            L += [f"{ind}    " + ln for ln in vec_load(gs_, "ge", f"{p.out_off} + uc * {d3}")]
+            L.append(f"{ind}    const float hw = {flit(p.coef)} * inv_norm * we[{p.slot * MUL} + uc];")
+            L.append(f"{ind}    " + " ".join(f"g{k} *= hw;" for k in range(d3)))
+            byik: Dict[Tuple[int, int], List[Tuple[int, float]]] = {}
+            for (i, j, k), c in _path_cg(p):
+                byik.setdefault((i, k), []).append((j, c))
+            for (i, k), ts in sorted(byik.items()):
+                L.append(f"{ind}    {{ const float z = x{l}_{i} * g{k}; "
+                         + " ".join(f"a[{p.l2 * p.l2 + j}] = fmaf({flit(c)}, z, a[{p.l2 * p.l2 + j}]);"
+                                    for j, c in ts) + " }")
+            L.append(f"{ind}  }}")
+        L.append(f"{ind}}}")
+    if CG > 1:
+        L.append("  }")
+    elif LW < 32:
+        L.append("#pragma unroll")
+        L.append(f"  for (int q = 0; q < {nsh}; ++q) a[q] = act ? a[q] : 0.0f;")
+    L.append("  eelg_lane_reduce32(a);")
+    L.append(f"  if (live && u < {nshp}) gsh[(size_t)e * {nshp} + u] = a[0];")
+    L.append("}")
+    return "\n".join(L), nshp
 
 
 # ---------------------------------------------------------------------------
@@ -2491,11 +2618,23 @@ def main(outdir: str) -> None:
              "  return (eelg_f2r){v[2 * j], v[2 * j + 1]};",
              "}", ""]
     header = parts
+    # geometry gradients (their own translation unit, eelg_geom.hip): the SH gradient of every
+    # interaction set and the gradient of the SH evaluation
+    geom = ["// GENERATED by csrc/gen_kernels.py -- do not edit (included by eelg_geom.hip)",
+            "typedef float eelg_f4u __attribute__((ext_vector_type(4), aligned(4)));",
+            "typedef float eelg_f3u __attribute__((ext_vector_type(3), aligned(4)));",
+            "typedef float eelg_f2u __attribute__((ext_vector_type(2), aligned(4)));", ""]
+    geom += [emit_sh_bwd(lmax) for lmax in kernel_sets.LMAX]
+    geom_table = []
     global MUL
     for mul in kernel_sets.MULS:
         MUL = mul
         sfx = "" if mul == 32 else f"_m{mul}"
         parts = list(header)
+        for name, (node, sh, target) in tp_configs().items():
+            code, nshp = emit_tp_bwd_sh(name + sfx, node, sh, target)
+            geom.append(code)
+            geom_table.append((name + sfx, nshp))
         if mul == 32:
             for lmax in kernel_sets.LMAX:
                 parts.append(emit_sh(lmax))
@@ -2550,6 +2689,17 @@ def main(outdir: str) -> None:
                 f.write(src)
         print(f"wrote {path}: {len(src.splitlines())} lines")
     MUL = kernel_sets.MUL
+    geom.append("\n// ===== SH-gradient kernels by config name =====")
+    geom.append("static const eelg_tp_sh_cfg kTpShConfigs[] = {")
+    geom += [f'  {{"{name}", {nshp}, tp_bwd_sh_{name}}},' for name, nshp in geom_table]
+    geom.append("};")
+    src = "\n".join(geom) + "\n"
+    path = os.path.join(outdir, "eelg_gen_geom.hip")
+    old = open(path).read() if os.path.exists(path) else None
+    if old != src:
+        with open(path, "w") as f:
+            f.write(src)
+    print(f"wrote {path}: {len(src.splitlines())} lines")
 
 
 if __name__ == "__main__":

@@ -10,6 +10,7 @@ from .synthetic import SyntheticLattices, make_lattice  # noqa: F401
 from .data import Batch, Data, DataLoader, collate  # noqa: F401
 from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
+from .design import stiffness_sensitivity  # noqa: F401
 
 __all__ = ["GLAMM_Dataset", "EnergyEquivGNN"]
 classes = __all__

@@ -77,6 +77,11 @@ _SIGS = {
     "eelg_radial_fwd": ([_P, _I, _P, _P, _I, _P, _P, _P], _I),
     "eelg_radial_bwd_chain": ([_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "eelg_radial_bwd": ([_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    # geometry gradients
+    "eelg_tp_bwd_sh": ([_I, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P], _I),
+    "eelg_radial_bwd_x": ([_P, _I, _P, _P, _P, _P], _I),
+    "eelg_radial_bwd_gh": ([_P, _I, _I, _P, _P, _P, _P], _I),
+    "eelg_edge_embed_bwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P], _I),
 }
 
 LIN_MAXSRC, LIN_MAXSLOT, LINW_MAXINS = 4, 8, 8

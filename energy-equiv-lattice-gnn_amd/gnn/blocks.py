@@ -297,7 +297,12 @@ class TensorProductInteractionBlock(torch.nn.Module):
         if w is None:
             w = self.radial_weights(edge_feats)
         inv = 1.0 / self.agg_norm_const
-        if self.reduce in ("sum", "add"):
+        # geometry gradients: the fused / chunked backwards return no SH gradient
+        # (bf16 storage: the model refuses at its first forward, ops._tp_bwd_sh at the kernel)
+        geom = torch.is_grad_enabled() and edge_attrs.requires_grad
+        if self.reduce in ("sum", "add") and geom:
+            agg = ops.tp_interaction(x, edge_attrs, w, csr, idx, info, inv)
+        elif self.reduce in ("sum", "add"):
             if ops.TP_BWF and self._bwf(idx):
                 # output linear + TP with one fused backward kernel (eelg_tp_bwd_fused)
                 return ops.tp_interaction_linear(x, edge_attrs, w, csr, idx, info, inv, self.linear), None

@@ -84,7 +84,10 @@ class GNN_Head(torch.nn.Module):  # noqa: N801
         of the main stream (their backward runs on that stream too: autograd replays a
         backward op on its forward's stream and inserts the cross-stream waits).  Layer i
         waits for its own weights only."""
-        if not (ops.OVERLAP and edge_feats.is_cuda):
+        # geometry gradients (the edge features require grad): every layer computes its weights
+        # in line, so this path adds no cross-stream lifetimes to the tuned training step
+        geom = torch.is_grad_enabled() and edge_feats.requires_grad
+        if geom or not (ops.OVERLAP and edge_feats.is_cuda):
             return [None] * self.num_interactions, [None] * self.num_interactions
         main = torch.cuda.current_stream(edge_feats.device)
         side = ops.side_stream(edge_feats.device)
@@ -223,8 +226,15 @@ class EnergyEquivGNN(torch.nn.Module):
     def _forward(self, batch) -> Dict[str, torch.Tensor]:
         csr = self.edge_graph(batch)
         node_ft = _embed(self.node_ft_embedding, batch.node_attrs)
-        shifts = batch.shifts[csr.perm]
-        radius = batch.edge_attr[csr.perm].reshape(-1)
+        geom = torch.is_grad_enabled() and (batch.positions.requires_grad or batch.shifts.requires_grad
+                                            or batch.edge_attr.requires_grad)
+        if geom and storage_dtype(self.params) != torch.float32:
+            raise NotImplementedError(
+                "geometry gradients (positions / shifts / edge_attr requiring grad) are built for "
+                "fp32 storage only, not storage_dtype='bfloat16'")
+        # (with grad: the permutation's backward is a plain scatter, ops.permute_rows)
+        shifts = ops.permute_rows(batch.shifts, csr.perm)
+        radius = ops.permute_rows(batch.edge_attr, csr.perm).reshape(-1)
         edge_sh, edge_feats = ops.edge_embed(batch.positions, csr, shifts, radius, self.lmax,
                                              self.number_of_edge_basis, 0.6, self.max_edge_radius)
         c = self.stiffness_head(csr, node_ft, edge_sh, edge_feats, batch.batch, batch.num_graphs)

@@ -167,14 +167,22 @@ class EdgeCSR:
 
 
 # ---------------------------------------------------------------------------
-# edge embedding (no gradient: positions and radii are data)
+# edge embedding.  In training positions and radii are data and this is one launch
+# outside autograd; when any of them requires grad it is an autograd function whose backward
+# is eelg_edge_embed_bwd + two segment sums (geometry gradients)
 # ---------------------------------------------------------------------------
 def edge_embed(pos, csr: EdgeCSR, shifts_sorted, radius_sorted, lmax: int, nb: int,
                len_end: float, rad_end: float):
     _require_device(pos, shifts_sorted, radius_sorted)
-    if pos.requires_grad or shifts_sorted.requires_grad:
-        raise NotImplementedError("gradients w.r.t. positions are not part of the hot path "
-                                  "(the reference never differentiates through geometry)")
+    if torch.is_grad_enabled() and (pos.requires_grad or shifts_sorted.requires_grad
+                                    or radius_sorted.requires_grad):
+        return _EdgeEmbed.apply(pos, shifts_sorted, radius_sorted, csr, lmax, nb, float(len_end),
+                                float(rad_end))
+    return _edge_embed_fwd(pos, csr, shifts_sorted, radius_sorted, lmax, nb, len_end, rad_end)
+
+
+def _edge_embed_fwd(pos, csr: EdgeCSR, shifts_sorted, radius_sorted, lmax: int, nb: int,
+                    len_end: float, rad_end: float):
     e = csr.num_edges
     nsh = (lmax + 1) ** 2
     sh = torch.empty(e, sh_row_stride(nsh), device=pos.device, dtype=torch.float32)
@@ -185,6 +193,86 @@ def edge_embed(pos, csr: EdgeCSR, shifts_sorted, radius_sorted, lmax: int, nb: i
         _lib.ptr(_f32(shifts_sorted)), _lib.ptr(_f32(radius_sorted)), e, lmax, nb,
         float(len_end), float(rad_end), _lib.ptr(sh), _lib.ptr(feats), _lib.stream(sh)), "edge_embed")
     return sh[:, :nsh], feats          # [E, nsh] view of the padded rows the TP kernels read
+
+
+class _EdgeEmbed(torch.autograd.Function):
+    """``edge_embed`` over (positions, sorted shifts, sorted radii).  Backward: one thread per
+    edge turns (grad_sh, grad_feats) into the edge vector's gradient and the radius gradient
+    (``eelg_edge_embed_bwd``); the node gradient is the receiver sum minus the sender sum of the
+    edge-vector gradients (``eelg_segment_sum_csr`` twice: fixed order, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, pos, shifts_sorted, radius_sorted, csr: EdgeCSR, lmax, nb, len_end, rad_end):
+        pos, shifts_sorted, radius_sorted = _f32(pos), _f32(shifts_sorted), _f32(radius_sorted)
+        ctx.save_for_backward(pos, shifts_sorted, radius_sorted)
+        ctx.csr, ctx.args = csr, (lmax, nb, len_end, rad_end)
+        sh, feats = _edge_embed_fwd(pos, csr, shifts_sorted, radius_sorted, lmax, nb, len_end, rad_end)
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            # only the radii require grad: the SH do not depend on them, so they carry no grad and
+            # the layers launch no tp_bwd_sh for a gradient nobody reads
+            ctx.mark_non_differentiable(sh)
+        return sh, feats
+
+    @staticmethod
+    def backward(ctx, gsh, gfeats):
+        pos, shifts, radius = ctx.saved_tensors
+        csr = ctx.csr
+        lmax, nb, len_end, rad_end = ctx.args
+        e = csr.num_edges
+        gsh, gfeats = _strided_rows(gsh), _f32(gfeats)
+        gvec = torch.empty(e, 4, device=pos.device, dtype=torch.float32)
+        grad = torch.empty(e, device=pos.device, dtype=torch.float32)
+        tok = TIMER.start("edge_embed_bwd")
+        _lib.check(_lib.load().eelg_edge_embed_bwd(
+            _lib.ptr(pos), _lib.ptr(csr.sender), _lib.ptr(csr.receiver), _lib.ptr(shifts),
+            _lib.ptr(radius), e, lmax, nb, len_end, rad_end, _lib.ptr(gsh), int(gsh.stride(0)) if e else
+            (lmax + 1) ** 2, _lib.ptr(gfeats), _lib.ptr(gvec), _lib.ptr(grad), _lib.stream(gvec)),
+            "edge_embed_bwd")
+        TIMER.stop(tok)
+        gpos = None
+        if ctx.needs_input_grad[0]:
+            n = csr.num_nodes
+            if e:
+                gpos = (segment_sum_csr(gvec, csr.rowptr, n)
+                        - segment_sum_csr(gvec, csr.srowptr, n, idx=csr.sperm))[:, :3]
+            else:
+                gpos = torch.zeros_like(pos)
+        return (gpos, gvec[:, :3] if ctx.needs_input_grad[1] else None,
+                grad.view_as(radius) if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def _strided_rows(t: torch.Tensor) -> torch.Tensor:
+    """fp32 rows with unit column stride (a column slice of padded rows passes as it is)"""
+    if t.dtype != torch.float32:
+        raise TypeError(f"expected float32, got {t.dtype}")
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t
+    return t.contiguous()
+
+
+class _PermuteRows(torch.autograd.Function):
+    """``t[perm]`` for a permutation ``perm``; the backward writes every row back to its place
+    (a plain scatter without accumulation, where indexing's autograd runs an accumulating
+    index_put)."""
+
+    @staticmethod
+    def forward(ctx, t, perm):
+        ctx.save_for_backward(perm)
+        return t[perm]
+
+    @staticmethod
+    def backward(ctx, g):
+        (perm,) = ctx.saved_tensors
+        out = torch.empty_like(g)
+        out[perm] = g
+        return out, None
+
+
+def permute_rows(t: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """``t[perm]`` (``perm`` a permutation of the rows), differentiable without accumulation"""
+    if torch.is_grad_enabled() and t.requires_grad:
+        return _PermuteRows.apply(t, perm)
+    return t[perm]
 
 
 def sh_row_stride(nsh: int) -> int:
@@ -346,6 +434,8 @@ class _TPInteraction(torch.autograd.Function):
         e = csr.num_edges
         gw = torch.empty_like(w)                       # same storage type as w
         lib = _lib.load()
+        # the SH gradient (geometry gradients only): its own kernel, one padded row per edge
+        gsh = _tp_bwd_sh(ctx, x, w, g) if ctx.needs_input_grad[1] else None
         sender = TP_BWD_SENDER if TP_BWD_SENDER is not None else w.dtype == torch.bfloat16
         if sender:
             # sender-order pass: grad_x summed per sender in registers, no gxe round trip
@@ -357,7 +447,7 @@ class _TPInteraction(torch.autograd.Function):
                            _lib.ptr(g), float(ctx.inv_norm), _lib.ptr(gw), _lib.ptr(gx),
                            _lib.stream(gx)), "tp_bwd_sender")
             TIMER.stop(tok)
-            return gx, None, gw, None, None, None, None
+            return gx, gsh, gw, None, None, None, None
         gxe = torch.empty(e, info["din"], device=x.device, dtype=w.dtype)
         spos = csr.sender_pos() if TP_BWD_SPOS else None
         bwd = lib.eelg_tp_bwd_sorted_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_sorted
@@ -368,7 +458,24 @@ class _TPInteraction(torch.autograd.Function):
         TIMER.stop(tok)
         gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes,
                              idx=None if spos is not None else csr.sperm)
-        return gx, None, gw, None, None, None, None
+        return gx, gsh, gw, None, None, None, None
+
+
+def _tp_bwd_sh(ctx, x, w, g):
+    """``eelg_tp_bwd_sh``: grad of the interaction w.r.t. its SH operand, [E, nsh] (a view of the
+    padded rows the kernel writes, pad = 0)"""
+    csr, info = ctx.csr, ctx.info
+    if w.dtype != torch.float32:
+        raise NotImplementedError("the SH gradient of the interaction takes fp32 TP weights; "
+                                  "bf16 storage (storage_dtype='bfloat16') has no geometry gradients")
+    e, nsh = csr.num_edges, info["nsh"]
+    gsh = torch.empty(e, sh_row_stride(nsh), device=x.device, dtype=torch.float32)
+    tok = TIMER.start(f"tp_bwd_sh[din={info['din']}]")
+    _lib.check(_lib.load().eelg_tp_bwd_sh(
+        ctx.cfg, _lib.ptr(x), None, _lib.ptr(w), _lib.ptr(csr.sender), _lib.ptr(csr.receiver), e,
+        _lib.ptr(g), float(ctx.inv_norm), _lib.ptr(gsh), _lib.stream(gsh)), "tp_bwd_sh")
+    TIMER.stop(tok)
+    return gsh[:, :nsh]
 
 
 def tp_interaction(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: float):
@@ -880,9 +987,12 @@ class _RadialMLP(torch.autograd.Function):
     """Linear(+bias)-SiLU-...-Linear(no bias) on edge features as one fused HIP kernel
     (``eelg_radial_fwd``: hidden layers on fp32 MFMA, the output layer fp32-accurate on bf16
     MFMA with split operands, hidden activations in LDS, only the pre-activations and the
-    [E, W] output reach HBM), backward as three (``eelg_radial_bwd``).  No grad w.r.t.
-    the features, which come from eelg_edge_embed without grad.  Edge sets past
-    the kernels' 2 GiB per-stream limit run as several launches (``_radial_chunks``)."""
+    [E, W] output reach HBM), backward as three (``eelg_radial_bwd``).  The features carry no
+    grad in training (they come from eelg_edge_embed); when they do (geometry
+    gradients) one more launch, ``eelg_radial_bwd_x``, walks the hidden layers back from the
+    grad_h the backward leaves, and with every weight frozen the weight-gradient launches are
+    skipped (``eelg_radial_bwd_gh`` alone).  Edge sets past the kernels' 2 GiB per-stream limit
+    run as several launches (``_radial_chunks``)."""
 
     @staticmethod
     def forward(ctx, feats, out_dtype, *params):
@@ -937,8 +1047,21 @@ class _RadialMLP(torch.autograd.Function):
         lib = _lib.load()
         wot_parts = split_bf16x3(wo.t().contiguous())             # [3, hidden, n_out]
         h = d.hidden
+        # grad of the features (geometry gradients only), filled per chunk from its grad_h
+        gfe = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
+        if not any(ctx.needs_input_grad[2:]):
+            # every weight frozen: grad_h = grad_w W_o alone, then the chain down to the features
+            for (a, b), z in zip(ctx.chunks, zs):
+                if gfe is None or b == a:
+                    continue
+                grad_h = torch.empty(b - a, h, device=g.device, dtype=torch.float32)
+                _lib.check(lib.eelg_radial_bwd_gh(_lib.ptr(g[a:b]), int(g.dtype == torch.bfloat16), b - a,
+                                                  ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(grad_h),
+                                                  _lib.stream(g)), "radial_bwd_gh")
+                _radial_bwd_x(grad_h, d, z, gfe[a:b])
+            return (gfe, None) + (None,) * len(params)
         if RADIAL_CHAIN and h == 64:
-            return _RadialMLP._backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out)
+            return _RadialMLP._backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out, gfe)
         n_small = h * nf + h + (d.n_hidden - 1) * (h * h + h)
         small, gwo = None, None
         for (a, b), z in zip(ctx.chunks, zs):
@@ -956,6 +1079,8 @@ class _RadialMLP(torch.autograd.Function):
                                            ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z),
                                            _lib.ptr(feats[a:b]), _lib.ptr(grad_h), _lib.ptr(part_h),
                                            _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd")
+            if gfe is not None and ec:
+                _radial_bwd_x(grad_h, d, z, gfe[a:b])
             sm, wo = sum_rows(part_h), sum_rows(part_wo)
             small = sm if small is None else small + sm
             gwo = wo if gwo is None else gwo + wo
@@ -964,10 +1089,10 @@ class _RadialMLP(torch.autograd.Function):
             grads.append(small[off: off + p.numel()].view_as(p))
             off += p.numel()
         grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
-        return (None, None, *grads)
+        return (gfe, None, *grads)
 
     @staticmethod
-    def _backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out):
+    def _backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out, gfe=None):
         """``eelg_radial_bwd_chain``: the kernels leave gz_n and the hidden-layer inputs; the
         weight gradients gz_n^T h_n are long-K reductions on the linear weight-gradient kernel and
         the bias gradients column sums (``eelg_sum_rows``), all in a fixed order"""
@@ -991,6 +1116,8 @@ class _RadialMLP(torch.autograd.Function):
                                                  ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z),
                                                  _lib.ptr(grad_h), _lib.ptr(gz), _lib.ptr(hin),
                                                  _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd_chain")
+            if gfe is not None and ec:
+                _radial_bwd_x(grad_h, d, z, gfe[a:b])
             for n in range(nh):
                 x_n = feats[a:b] if n == 0 else hin[n - 1]
                 gw = dense.linear_bwd_w(x_n, gz[n]) if ec else torch.zeros_like(params[2 * n])
@@ -1001,7 +1128,16 @@ class _RadialMLP(torch.autograd.Function):
             gwo = wo if gwo is None else gwo + wo
         grads = [t.view_as(p) for t, p in zip(acc, params[:-1])]
         grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
-        return (None, None, *grads)
+        return (gfe, None, *grads)
+
+
+def _radial_bwd_x(grad_h, d, z, out) -> None:
+    """``eelg_radial_bwd_x`` of one edge chunk: ``out`` [E_c, n_feat] rows of the feature gradient"""
+    tok = TIMER.start("radial_bwd_x")
+    _lib.check(_lib.load().eelg_radial_bwd_x(_lib.ptr(grad_h), grad_h.shape[0], ctypes.byref(d),
+                                             _lib.ptr(z), _lib.ptr(out), _lib.stream(out)),
+               "radial_bwd_x")
+    TIMER.stop(tok)
 
 
 def radial_mlp(feats: torch.Tensor, mlp: torch.nn.Sequential,

@@ -108,7 +108,10 @@ segment_sum_csr.register_autograd(_seg_backward, setup_context=_seg_setup)
 
 class _Ctx:
     """Stand-in for an autograd ctx: lets the custom ops reuse ``ops._TPInteraction``'s
-    forward / backward bodies (one launch sequence, not two copies of it)."""
+    forward / backward bodies (one launch sequence, not two copies of it).  The ops return no SH
+    gradient (``gnn.ops.tp_interaction`` is the entry that does), so the stand-in asks for none."""
+
+    needs_input_grad = (True, False, True, False, False, False, False)
 
     def save_for_backward(self, *ts):
         self.saved_tensors = ts

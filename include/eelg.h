@@ -388,6 +388,45 @@ int eelg_radial_bwd_chain(const void* grad_w, int grad_bf16, int n_edges, const 
                           const void* wot_parts, const float* zsave, float* grad_h, float* gz,
                           float* hin, float* part_wo, void* stream);
 
+/* ---- Geometry gradients: d stiffness / d (positions, shifts, strut radii) -------------------
+ * The reference model is plain differentiable torch, so autograd through its embedding
+ * (gnn/model.py:139-157), conv_tp_weights (gnn/blocks.py:590) and conv_tp + scatter
+ * (gnn/blocks.py:591-597) gives these; here they are three launches, all deterministic (no
+ * atomics), used only when the geometry requires grad. */
+
+/* SH gradient of eelg_tp_fwd (the reference call site gnn/blocks.py:591-597, differentiated
+ * w.r.t. edge_attrs):
+ *   grad_sh[e, l2^2 + j] = inv_norm * sum_{p with that l2} coef_p * sum_u w[e, p, u] *
+ *       sum_{i,k} C_p[i,j,k] * x[sender(e), l1, u, i] * grad_agg[receiver(e), p, u, k].
+ * grad_sh is [E, nshp] (rows padded to 16 bytes as the SH rows; the pad is written as 0);
+ * sender / receiver are the receiver-sorted edges' ends; w is fp32.  sh is not read (the TP is
+ * linear in it) and may be NULL.  -2 for a config without the kernel; no-op for n_edges == 0. */
+int eelg_tp_bwd_sh(int cfg, const float* x, const float* sh, const float* w, const int* sender,
+                   const int* receiver, int n_edges, const float* grad_agg, float inv_norm,
+                   float* grad_sh /* [E, nshp] */, void* stream);
+
+/* Input gradient of the radial MLP (conv_tp_weights, gnn/blocks.py:590): from grad_h[E, hidden]
+ * (= grad_w W_o, as eelg_radial_bwd / eelg_radial_bwd_chain / eelg_radial_bwd_gh leave it) and
+ * the saved pre-activations zsave[n_hidden, E, hidden], gz_n = grad_h_n SiLU'(z_n),
+ * grad_h_{n-1} = gz_n W_n, grad_feats[E, n_feat] = gz_0 W_0.  Same shapes as the forward. */
+int eelg_radial_bwd_x(const float* grad_h, int n_edges, const eelg_radial_desc* d,
+                      const float* zsave, float* grad_feats, void* stream);
+/* grad_h[E, hidden] = grad_w W_o alone (the first kernel of eelg_radial_bwd): what
+ * eelg_radial_bwd_x needs when no weight of the MLP requires a gradient. */
+int eelg_radial_bwd_gh(const void* grad_w, int grad_bf16, int n_edges, const eelg_radial_desc* d,
+                       const void* wot_parts, float* grad_h, void* stream);
+
+/* Backward of eelg_edge_embed (gnn/model.py:139-157 differentiated w.r.t. the edge vector and
+ * the radius): from grad_sh[E, grad_sh_ld] (row stride >= (lmax+1)^2) and grad_feats[E, 2*nb],
+ * grad_vec[E, 4] = [d/d vx, d/d vy, d/d vz, 0] (16-byte aligned) with v = pos[recv] - pos[send] +
+ * shift, and grad_radius[E].  The caller sums grad_vec per receiver minus per sender
+ * (eelg_segment_sum_csr) for the node gradient; grad_vec itself is the shifts' gradient. */
+int eelg_edge_embed_bwd(const float* pos, const int* sender, const int* receiver,
+                        const float* shifts, const float* radius, int n_edges, int lmax, int nb,
+                        float len_end, float rad_end, const float* grad_sh, int grad_sh_ld,
+                        const float* grad_feats, float* grad_vec, float* grad_radius,
+                        void* stream);
+
 /* Deterministic sum over the leading dimension of partial results (the partial buffers of
  * eelg_linear_bwd_w, eelg_radial_bwd and eelg_sc_bwd_coef, and the bias gradients = column
  * sums of grad_out; replaces the reference's implicit autograd reductions, gnn/blocks.py and

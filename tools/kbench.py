@@ -108,6 +108,23 @@ def main():
     rec("edge_embed", timeit_if("edge_embed", lambda: ops.edge_embed(b.positions, csr, b.shifts[csr.perm],
                                                      b.edge_attr[csr.perm].reshape(-1), 4, 6, 0.6, 0.05),
                              args.reps))
+    lib = ops._lib.load()
+    # geometry gradients: backward of the edge embedding (reads pos / ends / shift / radius and the
+    # two cotangent rows, writes the [E, 4] edge-vector gradient and the radius gradient)
+    gsh_in = torch.randn(e, 28, device=dev)
+    gft_in = torch.randn(e, 12, device=dev)
+    gvec = torch.empty(e, 4, device=dev)
+    grad_r = torch.empty(e, device=dev)
+    pos32 = b.positions.contiguous()
+    sh_s, rad_s = b.shifts[csr.perm].contiguous(), b.edge_attr[csr.perm].reshape(-1).contiguous()
+
+    def eeb():
+        ops._lib.check(lib.eelg_edge_embed_bwd(
+            ops._lib.ptr(pos32), ops._lib.ptr(csr.sender), ops._lib.ptr(csr.receiver), ops._lib.ptr(sh_s),
+            ops._lib.ptr(rad_s), e, 4, 6, 0.6, 0.05, ops._lib.ptr(gsh_in), 28, ops._lib.ptr(gft_in),
+            ops._lib.ptr(gvec), ops._lib.ptr(grad_r), ops._lib.stream(gvec)), "edge_embed_bwd")
+    rec("edge_embed_bwd", timeit_if("edge_embed_bwd", eeb, args.reps),
+        4 * (3 * n + 2 * e + 3 * e + e + 28 * e + 12 * e + 4 * e + e))
     blk = TensorProductInteractionBlock(hid, sh_ir, "12x0e", hid, 4.0).to(dev)
     idx, info = blk._config()
     x = torch.randn(n, 800, device=dev)
@@ -120,7 +137,6 @@ def main():
     g = torch.randn_like(agg)
     gw = torch.empty_like(w)
     gxe = torch.empty(e, 800, device=dev)
-    lib = ops._lib.load()
 
     def tpb():
         ops._lib.check(lib.eelg_tp_bwd(idx, ops._lib.ptr(x), ops._lib.ptr(sh), ops._lib.ptr(w),
@@ -129,6 +145,17 @@ def main():
                                        ops._lib.stream(x)), "tp_bwd")
     bwd_bytes = 4 * (n * 800 + e * 25 + 2 * e * info["wn"] + 2 * e + e * 800 + n * info["dmid"])
     rec("tp_bwd (B)", timeit_if("tp_bwd (B)", tpb, args.reps), bwd_bytes, 2 * tp_flops)
+    # geometry gradients: the interaction's SH gradient reads the rows tp_bwd reads (without the
+    # SH) and writes one padded 28-float row per edge instead of grad_w + gxe
+    gsh = torch.empty(e, 28, device=dev)
+
+    def tpsh():
+        ops._lib.check(lib.eelg_tp_bwd_sh(idx, ops._lib.ptr(x), None, ops._lib.ptr(w),
+                                          ops._lib.ptr(csr.sender), ops._lib.ptr(csr.receiver), e,
+                                          ops._lib.ptr(g), 0.25, ops._lib.ptr(gsh), ops._lib.stream(x)),
+                       "tp_bwd_sh")
+    sh_bytes = 4 * (n * 800 + e * info["wn"] + 2 * e + e * 28 + n * info["dmid"])
+    rec("tp_bwd_sh (B)", timeit_if("tp_bwd_sh (B)", tpsh, args.reps), sh_bytes, tp_flops)
     # fused output-linear grad-x + TP backward (replaces lin 7360->800 bwd_x + tp_bwd)
     gyl = torch.randn(n, 800, device=dev)
     lw = blk.linear.weight.detach().contiguous()
@@ -207,6 +234,19 @@ def main():
         out = ops.radial_mlp(efn, mlp)
         out.backward(torch.ones_like(out))
     rec("radial fwd+bwd (HIP)", timeit_if("radial fwd+bwd (HIP)", radfb, args.reps), None, 3 * rad_fl)
+    # geometry gradients: the MLP's input gradient from grad_h and the saved pre-activations
+    zs = torch.randn(2, e, 64, device=dev)
+    gh = torch.randn(e, 64, device=dev)
+    gfe = torch.empty(e, 12, device=dev)
+    rdesc = ops._radial_desc([p.detach() for p in mlp.parameters()], 12)
+    rdesc.n_out = -(-rdesc.n_out // 8) * 8
+
+    def radbx():
+        import ctypes
+        ops._lib.check(lib.eelg_radial_bwd_x(ops._lib.ptr(gh), e, ctypes.byref(rdesc), ops._lib.ptr(zs),
+                                             ops._lib.ptr(gfe), ops._lib.stream(gfe)), "radial_bwd_x")
+    rec("radial_bwd_x", timeit_if("radial_bwd_x", radbx, args.reps), 4 * e * (64 + 2 * 64 + 12),
+        2 * e * (64 * 64 + 64 * 12))
     rec("radial MLP fwd (torch)", timeit_if("radial MLP fwd (torch)", lambda: mlp(ef), args.reps), None,
         2 * e * (12 * 64 + 64 * 64 + 64 * info["wn"]))
 
@@ -215,6 +255,29 @@ def main():
         out.backward(torch.ones_like(out))
     rec("radial MLP fwd+bwd (nn.Sequential)", timeit_if("radial MLP fwd+bwd (torch)", mlpfb, args.reps), None,
         3 * 2 * e * (12 * 64 + 64 * 64 + 64 * info["wn"]))
+    if want("stiffness_sensitivity") or want("training fwd+bwd"):
+        # the bench model (4 layers, lmax 4, correlation 3): one design-sensitivity call
+        # (gnn.design.stiffness_sensitivity: forward + geometry backward, parameters frozen) next
+        # to one training forward + loss + backward of the same model and batch
+        from argparse import Namespace
+        from gnn import EnergyEquivGNN, stiffness_sensitivity
+        from gnn.train import stiffness_loss
+        ro = "16x0e+16x1o+16x2e+16x3o+16x4e"
+        p = Namespace(lmax=4, hidden_irreps=hid, readout_irreps=ro, num_edge_bases=6,
+                      interaction_reduction="sum", interaction_bias=True, agg_norm_const=4.0,
+                      inter_MLP_dim=64, inter_MLP_layers=3, correlation=3, global_reduction="mean",
+                      message_passes=4, positive_function="matrix_power_2",
+                      max_edge_radius=ds.max_edge_radius)
+        torch.manual_seed(0)
+        model = EnergyEquivGNN(p).to(dev)
+
+        def train():
+            model.zero_grad(set_to_none=True)
+            stiffness_loss(model(b)["stiffness"], b.stiffness).backward()
+        rec("training fwd+bwd (config 2)", timeit_if("training fwd+bwd (config 2)", train, args.reps))
+        model.zero_grad(set_to_none=True)
+        rec("stiffness_sensitivity (config 2)",
+            timeit_if("stiffness_sensitivity (config 2)", lambda: stiffness_sensitivity(model, b), args.reps))
     print(json.dumps(res))
 
 
