@@ -454,6 +454,36 @@ const eelg_sc_cfg* eelg_sc_table_mul(int mul, int* n) {
   }
 }
 
+static const eelg_sc_cfg* sc_live_table_mul(int mul, int* n) {
+  switch (mul) {
+    case 16: return eelg_sc_live_table_m16(n);
+    case 32: return eelg_sc_live_table_m32(n);
+    case 64: return eelg_sc_live_table_m64(n);
+    default: *n = 0; return nullptr;
+  }
+}
+
+// one index space per channel count: the full sets, then the live-output sets
+const eelg_sc_cfg* eelg_sc_at(int mul, int cfg) {
+  int n = 0, nl = 0;
+  const eelg_sc_cfg* t = eelg_sc_table_mul(mul, &n);
+  if (!t || cfg < 0) return nullptr;
+  if (cfg < n) return &t[cfg];
+  const eelg_sc_cfg* tl = sc_live_table_mul(mul, &nl);
+  return (tl && cfg - n < nl) ? &tl[cfg - n] : nullptr;
+}
+
+// the output l list of a set: the recorded one, or 0 .. lmax with (lmax + 1)^2 = D
+static int sc_outputs(const eelg_sc_cfg& c, int* ls) {
+  if (c.nout > 0) {
+    for (int i = 0; i < c.nout; ++i) ls[i] = c.out_l[i];
+    return c.nout;
+  }
+  int n = 0;
+  while (n * n < c.D) ls[n] = n, ++n;
+  return n;
+}
+
 extern "C" {
 
 const char* eelg_version(void) { return EELG_VERSION; }
@@ -479,22 +509,46 @@ int eelg_tp_info(int cfg, int* info, uint64_t* sig) {
 }
 
 int eelg_sc_find(const char* name) {
-  int n = 0;
-  const eelg_sc_cfg* t = eelg_sc_table(&n);
-  for (int i = 0; i < n; ++i)
-    if (strcmp(t[i].name, name) == 0) return i;
+  for (int i = 0; const eelg_sc_cfg* c = eelg_sc_at(32, i); ++i)
+    if (strcmp(c->name, name) == 0) return i;
   return fail(-1, "unknown symmetric-contraction config '%s'", name);
 }
 
 int eelg_sc_info(int cfg, int* info, uint64_t* sig) {
-  int n = 0;
-  const eelg_sc_cfg* t = eelg_sc_table(&n);
-  if (cfg < 0 || cfg >= n) return fail(-1, "bad sc config %d", cfg);
-  const eelg_sc_cfg& c = t[cfg];
+  const eelg_sc_cfg* cp = eelg_sc_at(32, cfg);
+  if (!cp) return fail(-1, "bad sc config %d", cfg);
+  const eelg_sc_cfg& c = *cp;
   info[0] = c.D; info[1] = c.drow; info[2] = c.orow; info[3] = c.nterms; info[4] = c.njg;
   info[5] = c.Dout; info[6] = c.nbc; info[7] = c.cld;
   *sig = c.sig;
   return 0;
+}
+
+int eelg_sc_outputs(int cfg, int* ls8) {
+  const eelg_sc_cfg* c = eelg_sc_at(32, cfg);
+  if (!c) return fail(-1, "bad sc config %d", cfg);
+  return sc_outputs(*c, ls8);
+}
+
+int eelg_sc_find_outputs(int cfg, const int* ls, int n_ls) {
+  const eelg_sc_cfg* base = eelg_sc_at(32, cfg);
+  if (!base) return fail(-1, "bad sc config %d", cfg);
+  if (n_ls <= 0 || n_ls > 8) return fail(-2, "sc_find_outputs: %d output l", n_ls);
+  // the same coupling and correlation = the same name up to the output suffix ("_o024")
+  const char* us = strstr(base->name, "_o");
+  const size_t stem = us ? (size_t)(us - base->name) : strlen(base->name);
+  for (int i = 0; const eelg_sc_cfg* c = eelg_sc_at(32, i); ++i) {
+    const char* cu = strstr(c->name, "_o");
+    const size_t cstem = cu ? (size_t)(cu - c->name) : strlen(c->name);
+    if (cstem != stem || strncmp(c->name, base->name, stem) != 0) continue;
+    int have[8];
+    if (sc_outputs(*c, have) != n_ls) continue;
+    bool same = true;
+    for (int k = 0; k < n_ls; ++k) same = same && have[k] == ls[k];
+    if (same) return i;
+  }
+  return fail(-1, "no symmetric-contraction set of '%.*s' with these %d output l", (int)stem,
+              base->name, n_ls);
 }
 
 int eelg_edge_embed(const float* pos, const int* sender, const int* receiver, const float* shifts,
@@ -865,8 +919,17 @@ static const eelg_sc_cfg* sc_get(int cfg, int mul) {
   int n = 0;
   const eelg_sc_cfg* t = eelg_sc_table_mul(mul, &n);
   if (!t) { fail(-2, "symmetric contraction built for mul 16 / 32 / 64, got %d", mul); return nullptr; }
-  if (cfg < 0 || cfg >= n) { fail(-1, "bad sc config %d", cfg); return nullptr; }
-  return &t[cfg];
+  const eelg_sc_cfg* c = eelg_sc_at(mul, cfg);
+  if (!c) fail(-1, "bad sc config %d", cfg);
+  return c;
+}
+
+// the row widths a caller states for a set's buffers ([N, mul * D] in, [N, mul * Dout] out)
+static int sc_check_rows(const eelg_sc_cfg* c, int mul, int x_row, int out_row, const char* what) {
+  if (x_row != mul * c->D || out_row != mul * c->Dout)
+    return fail(-2, "%s: set '%s' at mul %d reads rows of %d and writes rows of %d floats, got %d / %d",
+                what, c->name, mul, mul * c->D, mul * c->Dout, x_row, out_row);
+  return 0;
 }
 
 int eelg_gate_fwd(const float* x, int n_nodes, const eelg_gate_desc* desc, float cst, float* y,
@@ -908,6 +971,23 @@ int eelg_sc_fwd(int cfg, const float* x, const float* coef, int n_nodes, int mul
   return check_launch("sc_fwd");
 }
 
+int eelg_sc_fwd_rows(int cfg, const float* x, int x_row, const float* coef, int n_nodes, int mul,
+                     float* out, int out_row, void* stream) {
+  const eelg_sc_cfg* c = sc_get(cfg, mul);
+  if (!c) return -1;
+  if (int rc = sc_check_rows(c, mul, x_row, out_row, "sc_fwd")) return rc;
+  return eelg_sc_fwd(cfg, x, coef, n_nodes, mul, out, stream);
+}
+
+int eelg_sc_bwd_x_rows(int cfg, const float* x, int x_row, const float* coef, const float* grad_out,
+                       int grad_row, int n_nodes, int mul, float* grad_x, float* xt, float* gt,
+                       void* stream) {
+  const eelg_sc_cfg* c = sc_get(cfg, mul);
+  if (!c) return -1;
+  if (int rc = sc_check_rows(c, mul, x_row, grad_row, "sc_bwd_x")) return rc;
+  return eelg_sc_bwd_x_cm(cfg, x, coef, grad_out, n_nodes, mul, grad_x, xt, gt, stream);
+}
+
 int eelg_sc_bwd_x(int cfg, const float* x, const float* coef, const float* grad_out, int n_nodes,
                   int mul, float* grad_x, void* stream) {
   return eelg_sc_bwd_x_cm(cfg, x, coef, grad_out, n_nodes, mul, grad_x, nullptr, nullptr, stream);
@@ -942,7 +1022,8 @@ int eelg_sc_cmajor(int cfg, int which, const float* x, int n_nodes, int mul, flo
 // of one-workgroup-per-CU blocks on the 256 CUs (lmax 4, correlation 3: 4 ranges; lmax 3:
 // 16), with ranges of at least 2048 nodes
 static int sc_coef_range(const eelg_sc_cfg& c, int n_nodes, int mul) {
-  const int per = mul * (c.csets > 0 ? c.csets : 1);
+  const int sets = c.rsets > 0 ? c.rsets : c.csets;   // a live-output set: its full set's ranges
+  const int per = mul * (sets > 0 ? sets : 1);
   int nr = (1024 + per - 1) / per;
   const int nmax = (n_nodes + 2047) / 2048;
   nr = nr > nmax ? nmax : nr;
@@ -982,11 +1063,28 @@ int eelg_sc_bwd_coef(int cfg, const float* xt, const float* gt, int n_nodes, int
   return check_launch("sc_bwd_coef");
 }
 
+// the residual layout of a descriptor (eelg.h: res_row / r_off): 0 = bad (a slot's block leaves
+// its row), 1 = valid, 2 = valid and float4-aligned (the fast and packed kernels' loads)
+static int lin_res_layout(const eelg_lin_desc* desc) {
+  if (desc->res_row < 0) return 0;
+  if (desc->res_row == 0) return 2;   // y's layout: covered by the checks on y
+  bool al = (desc->res_row & 3) == 0;
+  for (int s = 0; s < desc->n_slots; ++s) {
+    const eelg_lin_slot& sl = desc->slot[s];
+    if (sl.r_off < 0) continue;
+    if (sl.r_off + sl.n_out * sl.d > desc->res_row) return 0;
+    al = al && (sl.r_off & 3) == 0;
+  }
+  return al ? 2 : 1;
+}
+
 int eelg_linear_fwd_res(const float* x, int x_row, const float* w, const float* bias,
                         const float* res, int n_nodes, float* y, int y_row,
                         const eelg_lin_desc* desc, void* stream) {
   if (!desc || desc->n_slots <= 0 || desc->n_slots > EELG_LIN_MAXSLOT)
     return fail(-2, "linear_fwd: bad descriptor");
+  const int rl = lin_res_layout(desc);
+  if (res && rl == 0) return fail(-2, "linear_fwd: a slot's residual block leaves the residual row");
   for (int s = 0; s < desc->n_slots; ++s) {
     const eelg_lin_slot& sl = desc->slot[s];
     if (sl.n_src < 0 || sl.n_src > EELG_LIN_MAXSRC || sl.d <= 0)
@@ -998,7 +1096,7 @@ int eelg_linear_fwd_res(const float* x, int x_row, const float* w, const float* 
   if (n_nodes <= 0) return 0;
   const bool full = lin_fwd_fast_ok(x, x_row, y, y_row, desc);
   const bool part = !full && !res && LINF_PARTIAL && lin_fwd_fast_ok(x, x_row, y, y_row, desc, true);
-  if ((full || part) && !(res && (reinterpret_cast<uintptr_t>(res) & 15))) {
+  if ((full || part) && !(res && ((reinterpret_cast<uintptr_t>(res) & 15) || rl != 2))) {
     // groups of 32/d whole nodes; the d = 9 slots have the most (ceil(n / 3))
     int max_groups = 0;
     for (int s = 0; s < desc->n_slots; ++s) {
@@ -1091,6 +1189,9 @@ int eelg_linear_fwd_pk(const float* x, int x_row, const void* pack, const float*
       (reinterpret_cast<uintptr_t>(pack) & 15))
     return fail(-2, "linear_fwd_pk: the descriptor / rows do not qualify for the packed path "
                     "(whole 32-wide K chunks and column tiles, d odd <= 9, 16-B aligned rows)");
+  if (res && desc->res_row != 0)
+    return fail(-2, "linear_fwd_pk: the packed kernel adds a residual in y's layout only "
+                    "(desc->res_row = 0); eelg_linear_fwd_res takes the others");
   for (int s = 0; s < desc->n_slots; ++s)
     if (desc->slot[s].bias_off >= 0 && desc->slot[s].d != 1)
       return fail(-2, "linear_fwd_pk: bias on a non-scalar slot");

@@ -76,6 +76,14 @@ struct eelg_sc_cfg {
   int cld;                       // coefficient row stride (nterms rounded up to 16: 64-B aligned rows)
   eelg_sc_bwdc_fn bwd_coefs;     // streaming coefficient gradient (round 6; nullptr: bwd_coef's chunk form)
   int csets;                     // its term-group sets (workgroups per (channel, node range) tile)
+  // the output l list of a live-output set (out rows [N, mul * sum(2l+1)] in this order);
+  // nout = 0 (the full sets' initialisers stop before it): every l of the coupling, 0 .. lmax
+  int nout;
+  int out_l[8];
+  // term-group sets of the full set of the same coupling and correlation (0: csets): a live-output
+  // set splits the nodes of its coefficient gradient into the full set's node ranges, so every
+  // coefficient is summed over the same partials whichever of the two sets computes it
+  int rsets;
 };
 
 // every generated tensor-product set, all channel counts (eelg_capi.hip merges the per-mul tables
@@ -102,6 +110,13 @@ const eelg_sc_cfg* eelg_sc_table_mul(int mul, int* n);
 const eelg_sc_cfg* eelg_sc_table_m16(int* n);
 const eelg_sc_cfg* eelg_sc_table_m32(int* n);
 const eelg_sc_cfg* eelg_sc_table_m64(int* n);
+// the live-output sets (generated/eelg_gen_live_m*.hip); their config indices follow the full
+// sets' (eelg_sc_at)
+const eelg_sc_cfg* eelg_sc_live_table_m16(int* n);
+const eelg_sc_cfg* eelg_sc_live_table_m32(int* n);
+const eelg_sc_cfg* eelg_sc_live_table_m64(int* n);
+// config ``cfg`` of channel count ``mul`` over both tables (nullptr: out of range or no such mul)
+const eelg_sc_cfg* eelg_sc_at(int mul, int cfg);
 
 // fp32-accurate GEMM operands on bf16 MFMA ("x6"): an fp32 value splits EXACTLY into three bf16
 // parts by truncation, x = p0 + p1 + p2 (p0 = the top 8 significant bits, p1 the next 8 of the

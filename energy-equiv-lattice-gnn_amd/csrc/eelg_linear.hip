@@ -209,9 +209,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_FWD_WPE
     const int olen = jw * d;  // floats per node in this column tile
     float* __restrict__ yb = y + (size_t)n_lo * y_row + sl.y_off + (size_t)jt * 32 * d;
     // optional residual (same layout as y) added in the epilogue
-    const float* __restrict__ rb = res ? res + (size_t)n_lo * y_row + sl.y_off + (size_t)jt * 32 * d : nullptr;
+    // (its own row stride / slot offset when desc.res_row is set; r_off < 0: none for this slot)
+    const int r_row = desc.res_row ? desc.res_row : y_row;
+    const int r_off = desc.res_row ? sl.r_off : sl.y_off;
+    const float* __restrict__ rb = (res && r_off >= 0) ? res + (size_t)n_lo * r_row + r_off + (size_t)jt * 32 * d : nullptr;
     const bool vst = (y_row & 3) == 0 && (olen & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                     ((sl.y_off + jt * 32 * d) & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0;
+                     ((sl.y_off + jt * 32 * d) & 3) == 0 &&
+                     (!rb || ((reinterpret_cast<uintptr_t>(res) & 15) == 0 && (r_row & 3) == 0 && (r_off & 3) == 0));
     if (vst) {
       // float4 per-node runs; nodes cut by the workgroup's row range go element-wise
       Walk3 ow;
@@ -228,7 +232,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_FWD_WPE
             if (++m == d) { m = 0; ++jj; }
           }
           if (rb) {
-            const float4 r4 = *reinterpret_cast<const float4*>(rb + (dst - yb));
+            const float4 r4 = *reinterpret_cast<const float4*>(rb + (size_t)ow.a * r_row + ow.b * d + ow.m);
             v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w;
           }
           *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -236,7 +240,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_FWD_WPE
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int row = nrow0 + m;
-            if (row >= 0 && row < LIN_ROWS) dst[t] = Os[row * LIN_ST + jj] + (rb ? rb[(dst - yb) + t] : 0.0f);
+            if (row >= 0 && row < LIN_ROWS)
+              dst[t] = Os[row * LIN_ST + jj] + (rb ? rb[(size_t)ow.a * r_row + ow.b * d + ow.m + t] : 0.0f);
             if (++m == d) { m = 0; ++jj; }
           }
         }
@@ -249,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_FWD_WPE
         const int row = (n_lo + ow.a) * d + ow.m - r0;
         if (row >= 0 && row < LIN_ROWS) {
           const size_t o = (size_t)ow.a * y_row + ow.b * d + ow.m;
-          yb[o] = Os[row * LIN_ST + ow.b] + (rb ? rb[o] : 0.0f);
+          yb[o] = Os[row * LIN_ST + ow.b] + (rb ? rb[(size_t)ow.a * r_row + ow.b * d + ow.m] : 0.0f);
         }
         ow.next(jw, d);
       }
@@ -257,7 +262,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_FWD_WPE
   }
 }
 
-// grad W for each instruction: partial[p, w_off + u*n_out + j] =
+// grad W for each instruction (ldw: the weight block's row stride, 0 = n_out; a column range of
+// a wider block has ldw > n_out): partial[p, w_off + u*ldw + j] =
 //   alpha * sum_{nodes of slice p, m} x[n, x_off + u*d + m] * g[n, g_off + j*d + m]
 // One workgroup = (node slice, instruction, 32x32 (u, j) tile).  The four waves take
 // chunks of floor(32/d) whole nodes round-robin, stage their X[row][u] / G[row][j] tiles
@@ -416,7 +422,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN_BWDW_WP
     for (int i = 0; i < 16; ++i) {
       const float v = acc[i] + red[i * 64 + lane] + red[(16 + i) * 64 + lane] + red[(32 + i) * 64 + lane];
       const int uu = ut * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-      if (uu < K && j < NO) dst[(size_t)uu * NO + j] = v * in.alpha;
+      if (uu < K && j < NO) dst[(size_t)uu * (in.ldw ? in.ldw : NO) + j] = v * in.alpha;
     }
   }
 }
@@ -470,7 +476,7 @@ __global__ __launch_bounds__(256) void lin_bwdw_fast_kernel(const float* __restr
     for (int i = 0; i < 16; ++i) {
       const float v = acc[i] + red[i * 64 + lane] + red[(16 + i) * 64 + lane] + red[(32 + i) * 64 + lane];
       const int uu = ut * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-      dst[(size_t)uu * NO + j] = v * in.alpha;
+      dst[(size_t)uu * (in.ldw ? in.ldw : NO) + j] = v * in.alpha;
     }
   }
 }
@@ -561,13 +567,23 @@ typedef float linf_f4n __attribute__((ext_vector_type(4)));
 #else
 #define LINF_STORE(v, p) (*(p) = (v))
 #endif
+// the slot's block of the residual operand: y's layout (res_row = 0), or rows of desc.res_row
+// floats with the slot at r_off (r_off < 0: the slot adds no residual -> null)
+__device__ __forceinline__ const float* lin_res_slot(const eelg_lin_desc& desc, const eelg_lin_slot& sl,
+                                                     const float* __restrict__ res) {
+  if (!res) return nullptr;
+  if (!desc.res_row) return res + sl.y_off;
+  return sl.r_off >= 0 ? res + sl.r_off : nullptr;
+}
+
 template <int D, bool RES, bool PART>
 __device__ __forceinline__ void lin_fwd_fast(const float* __restrict__ x, int x_row,
                                              const float* __restrict__ bias, int n_nodes,
                                              float* __restrict__ y, int y_row,
                                              const eelg_lin_slot& sl, int g_base, int g_lim,
                                              int jt, const float* __restrict__ ws,
-                                             float* __restrict__ xw, const float* __restrict__ res) {
+                                             float* __restrict__ xw, const float* __restrict__ res,
+                                             int r_row) {
   // this wave's node groups: g_base + wave, g_base + wave + LINF_WAVES, ... < g_lim
   using G = LinfGeom<D>;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
@@ -650,15 +666,19 @@ __device__ __forceinline__ void lin_fwd_fast(const float* __restrict__ x, int x_
       float* __restrict__ yb = y + sl.y_off + (size_t)jt * 32 * D;
       // residual (same layout as y) added in the epilogue: all of a lane's residual loads are
       // issued before its first store (clamped rows, no branch around a load)
+      // (res: the slot's block of the residual rows, stride r_row; null: this slot adds none)
       float4 rr[G::NQ];
-      if (RES) {
-        const float* __restrict__ rb = res + sl.y_off + (size_t)jt * 32 * D;
+      if (RES && res) {
+        const float* __restrict__ rb = res + (size_t)jt * 32 * D;
 #pragma unroll
         for (int qq = 0; qq < G::NQ; ++qq) {
           const int f = min(lane + 64 * qq, G::NB * G::RUN4 - 1);
           const int a = f / G::RUN4, w4 = PART ? min(f - a * G::RUN4, jw4 - 1) : f - a * G::RUN4;
-          rr[qq] = *reinterpret_cast<const float4*>(rb + (size_t)min(n0 + a, n_nodes - 1) * y_row + 4 * w4);
+          rr[qq] = *reinterpret_cast<const float4*>(rb + (size_t)min(n0 + a, n_nodes - 1) * r_row + 4 * w4);
         }
+      } else if (RES) {
+#pragma unroll
+        for (int qq = 0; qq < G::NQ; ++qq) rr[qq] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
       for (int qq = 0; qq < G::NQ; ++qq) {
@@ -694,13 +714,13 @@ __device__ __forceinline__ void lin_fwd_fast_d(int d, const float* __restrict__ 
                                                float* __restrict__ y, int y_row,
                                                const eelg_lin_slot& sl, int g0, int g1, int jt,
                                                const float* __restrict__ ws, float* __restrict__ xw,
-                                               const float* __restrict__ res) {
+                                               const float* __restrict__ res, int r_row) {
   switch (d) {
-    case 1: lin_fwd_fast<1, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res); break;
-    case 3: lin_fwd_fast<3, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res); break;
-    case 5: lin_fwd_fast<5, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res); break;
-    case 7: lin_fwd_fast<7, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res); break;
-    default: lin_fwd_fast<9, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res); break;
+    case 1: lin_fwd_fast<1, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res, r_row); break;
+    case 3: lin_fwd_fast<3, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res, r_row); break;
+    case 5: lin_fwd_fast<5, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res, r_row); break;
+    case 7: lin_fwd_fast<7, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res, r_row); break;
+    default: lin_fwd_fast<9, RES, PART>(x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res, r_row); break;
   }
 }
 
@@ -742,7 +762,8 @@ __global__ __launch_bounds__(64 * LINF_WAVES) void lin_fwd_fast_kernel(
   __syncthreads();
   float* xw = reinterpret_cast<float*>(xw4) + (threadIdx.x >> 6) * LINF_XW;
   const int g0 = gb * LINF_WAVES * LINF_GPW, g1 = min(n_groups, g0 + LINF_WAVES * LINF_GPW);
-  lin_fwd_fast_d<RES, PART>(d, x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw, res);
+  lin_fwd_fast_d<RES, PART>(d, x, x_row, bias, n_nodes, y, y_row, sl, g0, g1, jt, ws, xw,
+                            lin_res_slot(desc, sl, res), desc.res_row ? desc.res_row : y_row);
 }
 
 // one column tile per slot (the 800 -> 800 linears): an LDS floor of 64 KB (two workgroups per

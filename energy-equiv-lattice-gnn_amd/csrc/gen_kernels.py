@@ -202,6 +202,18 @@ def sc_configs() -> Dict[str, Tuple[str, Tuple[int, ...], int]]:
     return out
 
 
+def sc_live_configs() -> Dict[str, Tuple[str, Tuple[int, ...], int]]:
+    """The live-output sets (kernel_sets.LIVE_OUT): the same couplings and correlations with
+    only the output l the stiffness head reads, e.g. ``sc_l4_c3_o024``.  They go to their own
+    translation units (generated/eelg_gen_live*.hip), so the full sets' text does not change."""
+    out = {}
+    for lmax in kernel_sets.LMAX:
+        for ls in kernel_sets.sc_output_lists(lmax)[1:]:
+            for corr in kernel_sets.CORRELATIONS:
+                out[kernel_sets.sc_set_name(lmax, corr, ls)] = (kernel_sets.coupling_str(lmax), ls, corr)
+    return out
+
+
 tp_signature = cg.tp_signature
 sc_signature = cg.sc_signature
 
@@ -2292,7 +2304,7 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
         L += code
         cstream, NBC = 1, SC_COEF_SC
     info = dict(D=D, Dout=Dout, drow=drow, orow=orow, nterms=nt, cld=cld, njg=len(groups), wpb=WPB, nbc=NBC, nb=NB, nth=NTH,
-                cmajor_out=cmajor_out, cstream=cstream, csets=csets,
+                cmajor_out=cmajor_out, cstream=cstream, csets=csets, ls=tuple(ls),
                 sig=fnv1a64(sc_signature(coupling, ls, corr)))
     return "\n".join(L), info
 
@@ -2581,6 +2593,26 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
 
 
 # ---------------------------------------------------------------------------
+def _sc_table_row(name: str, i: dict, outputs: bool = False) -> str:
+    """one eelg_sc_cfg initialiser; ``outputs``: with the set's output l list (the full sets
+    leave it empty = every l of the coupling) and the term-group sets of its full set (the node
+    ranges of the coefficient gradient follow those)"""
+    tail = (f', {len(i["ls"])}, {{{", ".join(str(l) for l in i["ls"])}}}, {i.get("rsets", 0)}'
+            if outputs else "")
+    return (f'  {{"{name}", {i["D"]}, {i["Dout"]}, {i["drow"]}, {i["orow"]}, {i["nterms"]}, {i["njg"]}, {i["wpb"]}, '
+            f'0x{i["sig"]:016x}ULL, sc_fwd_{name}, sc_bwd_x_{name}, sc_bwd_coef_{name}, sc_cmajor_{name}, '
+            f'{i["cmajor_out"]}, {i["nbc"]}, {i["nb"]}, {i["nth"]}, {i["cld"]}, '
+            f'{"sc_bwd_coefs_" + name if i["cstream"] else "nullptr"}, {i["csets"]}{tail}}},')
+
+
+def _write_if_changed(path: str, src: str) -> None:
+    old = open(path).read() if os.path.exists(path) else None
+    if old != src:
+        with open(path, "w") as f:
+            f.write(src)
+    print(f"wrote {path}: {len(src.splitlines())} lines")
+
+
 def main(outdir: str) -> None:
     os.makedirs(outdir, exist_ok=True)
     global _PKV
@@ -2674,10 +2706,7 @@ def main(outdir: str) -> None:
         parts.append("};")
         parts.append("static const eelg_sc_cfg kScConfigs[] = {")
         for name, i in sc_table:
-            parts.append(f'  {{"{name}", {i["D"]}, {i["Dout"]}, {i["drow"]}, {i["orow"]}, {i["nterms"]}, {i["njg"]}, {i["wpb"]}, '
-                         f'0x{i["sig"]:016x}ULL, sc_fwd_{name}, sc_bwd_x_{name}, sc_bwd_coef_{name}, sc_cmajor_{name}, '
-                         f'{i["cmajor_out"]}, {i["nbc"]}, {i["nb"]}, {i["nth"]}, {i["cld"]}, '
-                         f'{"sc_bwd_coefs_" + name if i["cstream"] else "nullptr"}, {i["csets"]}}},')
+            parts.append(_sc_table_row(name, i))
         parts.append("};")
         parts.append(f"const eelg_tp_cfg* eelg_tp_table_m{mul}(int* n) {{ *n = (int)(sizeof(kTpConfigs)/sizeof(kTpConfigs[0])); return kTpConfigs; }}")
         parts.append(f"const eelg_sc_cfg* eelg_sc_table_m{mul}(int* n) {{ *n = (int)(sizeof(kScConfigs)/sizeof(kScConfigs[0])); return kScConfigs; }}")
@@ -2688,6 +2717,21 @@ def main(outdir: str) -> None:
             with open(path, "w") as f:
                 f.write(src)
         print(f"wrote {path}: {len(src.splitlines())} lines")
+        # the live-output contraction sets of this channel count: their own translation unit
+        live = list(header)
+        live_table = []
+        for name, (coupling, ls, corr) in sc_live_configs().items():
+            code, info = emit_sc(name + sfx, coupling, ls, corr)
+            live.append(code)
+            lmax_c = max(ir.l for _, ir in Irreps(coupling))
+            info["rsets"] = dict(sc_table)[kernel_sets.sc_set_name(lmax_c, corr) + sfx]["csets"]
+            live_table.append((name + sfx, info))
+        live.append("\n// ===== config table =====")
+        live.append("static const eelg_sc_cfg kScLiveConfigs[] = {")
+        live += [_sc_table_row(name, i, outputs=True) for name, i in live_table]
+        live.append("};")
+        live.append(f"const eelg_sc_cfg* eelg_sc_live_table_m{mul}(int* n) {{ *n = (int)(sizeof(kScLiveConfigs)/sizeof(kScLiveConfigs[0])); return kScLiveConfigs; }}")
+        _write_if_changed(os.path.join(outdir, f"eelg_gen_live_m{mul}.hip"), "\n".join(live) + "\n")
     MUL = kernel_sets.MUL
     geom.append("\n// ===== SH-gradient kernels by config name =====")
     geom.append("static const eelg_tp_sh_cfg kTpShConfigs[] = {")

@@ -27,6 +27,10 @@ _SIGS = {
     "eelg_tp_info": ([_I, _P, _P], _I),
     "eelg_sc_find": ([ctypes.c_char_p], _I),
     "eelg_sc_info": ([_I, _P, _P], _I),
+    "eelg_sc_outputs": ([_I, _P], _I),
+    "eelg_sc_find_outputs": ([_I, _P, _I], _I),
+    "eelg_sc_fwd_rows": ([_I, _P, _I, _P, _I, _I, _P, _I, _P], _I),
+    "eelg_sc_bwd_x_rows": ([_I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
     "eelg_edge_embed": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P], _I),
     "eelg_tp_fwd": ([_I, _P, _P, _P, _P, _P, _I, _F, _P, _P], _I),
     "eelg_tp_bwd": ([_I, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
@@ -93,17 +97,17 @@ class LinSrc(ctypes.Structure):
 
 class LinSlot(ctypes.Structure):
     _fields_ = [("y_off", _I), ("n_out", _I), ("d", _I), ("bias_off", _I), ("n_src", _I),
-                ("src", LinSrc * LIN_MAXSRC)]
+                ("src", LinSrc * LIN_MAXSRC), ("r_off", _I)]
 
 
 class LinDesc(ctypes.Structure):
-    _fields_ = [("n_slots", _I), ("max_jt", _I), ("max_rows", _I), ("pad", _I),
+    _fields_ = [("n_slots", _I), ("max_jt", _I), ("max_rows", _I), ("res_row", _I),
                 ("slot", LinSlot * LIN_MAXSLOT)]
 
 
 class LinWIns(ctypes.Structure):
     _fields_ = [("x_off", _I), ("k", _I), ("g_off", _I), ("n_out", _I), ("d", _I), ("w_off", _I),
-                ("alpha", _F)]
+                ("alpha", _F), ("ldw", _I)]
 
 
 class LinWDesc(ctypes.Structure):
@@ -208,6 +212,15 @@ def sc_config(name: str) -> Tuple[int, Dict[str, int], int]:
     if idx < 0:
         check(idx, f"sc config {name}")
     return (idx,) + _sc_info(idx)
+
+
+def sc_outputs(idx: int) -> Tuple[int, ...]:
+    """the output l of contraction set ``idx``, in row order"""
+    ls = (ctypes.c_int * 8)()
+    n = load().eelg_sc_outputs(idx, ctypes.cast(ls, _P))
+    if n < 0:
+        check(n, f"sc outputs of config {idx}")
+    return tuple(ls[:n])
 
 
 def _tp_info(idx: int):

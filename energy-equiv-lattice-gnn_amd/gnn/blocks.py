@@ -115,8 +115,10 @@ class GeneralNonLinearReadoutBlock(torch.nn.Module):
         self.linear_1 = Linear(irreps_in, self.irreps_nonlin)
         self.linear_2 = Linear(self.equivariant_nonlin.irreps_out, irreps_out)
 
-    def forward(self, x):
-        return self.linear_2(self.equivariant_nonlin(self.linear_1(x)))
+    def forward(self, x, live: bool = False):
+        """``live``: the variants prepared by the modules' ``set_live`` (compact rows of the
+        irreps a later consumer reads; ``GNN_Head``), where there are any"""
+        return self.linear_2(self.equivariant_nonlin(self.linear_1(x, live=live), live=live), live=live)
 
 
 class Cart_4_to_Mandel(torch.nn.Module):  # noqa: N801
@@ -194,11 +196,13 @@ class EquivariantProductBlock(torch.nn.Module):
         self.symmetric_contractions = SymmetricContraction(node_feats_irreps, sc_out, correlation)
         self.linear = Linear(sc_out, target_irreps)
 
-    def forward(self, node_feats, sc, residual: Optional[torch.Tensor] = None, grad_mailbox=None):
+    def forward(self, node_feats, sc, residual: Optional[torch.Tensor] = None, grad_mailbox=None,
+                live: bool = False):
         """``residual``: the model's layer residual (``gnn/model.py:95``), added in the linear's
-        epilogue instead of by a separate pass."""
-        x = self.linear(self.symmetric_contractions(node_feats), residual=residual,
-                        grad_mailbox=grad_mailbox)
+        epilogue instead of by a separate pass.  ``live``: only the output irreps prepared by
+        ``restrict_outputs`` / ``set_live`` of the two submodules, as compact rows."""
+        x = self.linear(self.symmetric_contractions(node_feats, live=live), residual=residual,
+                        grad_mailbox=grad_mailbox, live=live)
         return x + sc if self.use_sc else x
 
 
@@ -336,9 +340,11 @@ class MACELayer(torch.nn.Module):
                                                product_correlation, use_sc=False)
 
     def forward(self, node_ft, edge_index: EdgeIndex, edge_sh, edge_scalars,
-                tp_weights: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None):
+                tp_weights: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                live: bool = False):
         """``residual`` (default none): returns ``residual + layer(node_ft)`` with the add fused
-        into the product block's linear (``GNN_Head`` passes ``h`` for ``h + layer_i(h)``)."""
+        into the product block's linear (``GNN_Head`` passes ``h`` for ``h + layer_i(h)``).
+        ``live``: the product block's live outputs only (``EquivariantProductBlock.forward``)."""
         csr, edge_sh, edge_scalars = as_csr(edge_index, node_ft.shape[0], edge_sh, edge_scalars)
         if tp_weights is not None and not isinstance(edge_index, ops.EdgeCSR):
             tp_weights = tp_weights[csr.perm]
@@ -347,4 +353,4 @@ class MACELayer(torch.nn.Module):
         mb = GradMailbox() if (RESIDUAL_GRAD_FUSED and residual is node_ft) else None
         node_ft, sc = self.interaction(node_ft, edge_sh, edge_scalars, csr, tp_weights=tp_weights,
                                        grad_mailbox=mb)
-        return self.product(node_ft, sc, residual=residual, grad_mailbox=mb)
+        return self.product(node_ft, sc, residual=residual, grad_mailbox=mb, live=live)

@@ -12,6 +12,9 @@ Reference ``params`` space (``gnn/model.py:31-42``, ``gnn/mace.py:112-177``): ``
   generated; correlation 4 (the reference's ``filter_ir_mid`` coupling) runs the table-driven
   kernels (``csrc/eelg_scg.hip``) for SH lmax <= 3 (``TABLE_LMAX``: at lmax 4 the reference's
   own ``U_matrix_4`` is a [9, 25, 25, 25, 25, K] tensor, gigabytes, and so is its host build);
+* live-output contraction sets (``LIVE_OUT``): for every SH lmax and correlation 1..3, the same
+  contraction with only the output l that the stiffness head reads from the last layer
+  (``sc_l4_c3_o024``); ``check_sc`` accepts exactly these output lists and the full ones;
 * ``mul`` (channels per irrep) in ``MULS``: one lane per channel in the interaction kernels, a
   half-wave per 32 channels (mul = 64: two channel groups; mul = 16: half a half-wave).  The
   reference default and the benchmark configurations are 32; bf16 storage of the edge tensors
@@ -27,6 +30,11 @@ LMAX = (1, 2, 3, 4)
 CORRELATIONS = (1, 2, 3)
 TABLE_CORRELATIONS = (4,)
 TABLE_LMAX = 3
+# the live-output contraction sets (generated beside the full ones, correlation 1..3): per SH
+# lmax, the output l that the stiffness head ``Linear(readout, "2x0e+2x2e+1x4e")`` can read
+# from the last layer (``model.live_output_irreps`` derives them from the module structure;
+# these are the lists the generator builds, not a rule the model applies)
+LIVE_OUT = {1: (0,), 2: (0, 2), 3: (0, 2), 4: (0, 2, 4)}
 
 
 def natural(l: int) -> str:
@@ -41,11 +49,28 @@ def coupling_str(lmax: int) -> str:
     return "+".join(natural(l) for l in range(lmax + 1))
 
 
+def sc_set_name(lmax: int, corr: int, ls: Tuple[int, ...] = None) -> str:
+    """``sc_l4_c3`` (every output l up to lmax) or ``sc_l4_c3_o024`` (the listed output l)"""
+    base = f"sc_l{lmax}_c{corr}"
+    if ls is None or tuple(ls) == tuple(range(lmax + 1)):
+        return base
+    return base + "_o" + "".join(str(l) for l in ls)
+
+
+def sc_output_lists(lmax: int) -> Tuple[Tuple[int, ...], ...]:
+    """the output l lists generated for a coupling lmax: all of them, and the live subset"""
+    full = tuple(range(lmax + 1))
+    live = LIVE_OUT.get(lmax)
+    return (full,) if live is None or live == full else (full, live)
+
+
 def supported_text() -> str:
     return (f"generated kernel sets: SH lmax in {LMAX} with hidden_irreps "
             f"'{hidden_irreps_str(1)}' .. '{hidden_irreps_str(4)}' (mul channels of every l up to "
             f"the SH lmax, mul in {MULS}), correlation in {CORRELATIONS}; correlation "
-            f"{TABLE_CORRELATIONS[0]} (table-driven) for SH lmax <= {TABLE_LMAX}")
+            f"{TABLE_CORRELATIONS[0]} (table-driven) for SH lmax <= {TABLE_LMAX}; contraction "
+            f"outputs: every l up to the SH lmax, or (correlation in {CORRELATIONS}) the live "
+            f"lists " + ", ".join(f"lmax {k}: l in {v}" for k, v in LIVE_OUT.items()))
 
 
 def mul_of(irreps) -> int:
@@ -73,8 +98,10 @@ def check_sc(irreps_in, ls: Tuple[int, ...], correlation: int) -> None:
     lmax = irreps_in.lmax
     mul = mul_of(irreps_in)
     ok = (lmax in LMAX and mul in MULS and str(irreps_in) == hidden_irreps_str(lmax, mul)
-          and tuple(ls) == tuple(range(lmax + 1))
-          and (correlation in CORRELATIONS or (correlation in TABLE_CORRELATIONS and lmax <= TABLE_LMAX)))
+          and tuple(ls) in sc_output_lists(lmax)
+          and (correlation in CORRELATIONS
+               or (correlation in TABLE_CORRELATIONS and lmax <= TABLE_LMAX
+                   and tuple(ls) == tuple(range(lmax + 1)))))
     if not ok:
         raise NotImplementedError(
             f"no HIP symmetric-contraction kernels for {irreps_in} -> l in {tuple(ls)}, "

@@ -113,6 +113,9 @@ class SymmetricContraction(torch.nn.Module):
         self.register_buffer("u_sym", torch.tensor(plan.ubig, dtype=torch.float32), persistent=False)
         self._cfg = None
         self._coupling, self._ls = coupling, ls
+        # the live-output form (restrict_outputs): its output l, their terms' rows of u_sym, the
+        # generated set's signature / config, the CSR of those rows
+        self._live = self._live_rows = self._live_sig = self._live_cfg = self._live_u_csr = None
         self._u_loaded = {}          # (l, nu) -> U adopted from a loaded state_dict (CPU f32)
         self._ahead = None           # (coef, event, stream) issued by coefficients_ahead
         self._register_state_dict_hook(SymmetricContraction._emit_reference_U)
@@ -178,12 +181,55 @@ class SymmetricContraction(torch.nn.Module):
                 fresh[:, k0: k0 + block.shape[1]] = torch.from_numpy(block)
             with torch.no_grad():
                 self.u_sym.copy_(fresh.to(self.u_sym))
-            self._u_csr = None
+            self._u_csr = self._live_u_csr = None
             self._u_loaded = loaded
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
                                       unexpected_keys, error_msgs)
 
-    def _config(self):
+    def restrict_outputs(self, ls) -> bool:
+        """Prepare the live-output form that ``forward(x, live=True)`` runs: the outputs ``ls``
+        only (a subset of the module's output l, in order) with the generated live-output set,
+        returning compact rows ``[N, mul * sum(2l+1 for l in ls)]``.  The live set's terms are
+        the full plan's terms with a live output, in the same order, so its coefficients are
+        the matching rows of ``u_sym @ W``: ``weight_matrix()`` and ``u_sym`` keep every weight
+        block, the dead blocks' columns are zero in those rows, and the dead
+        ``contractions.*.weights.*`` get exact zero gradients.  None or every l: no live form.
+        False (no live form) where no such set exists: the table-driven correlation 4, or a
+        list that was not generated.  A plain call always computes every output."""
+        self._live = self._live_rows = self._live_sig = self._live_cfg = self._live_u_csr = None
+        ls = self._ls if ls is None else tuple(ls)
+        if ls == self._ls:
+            return True
+        if self._table is not None or any(l not in self._ls for l in ls):
+            return False
+        try:
+            kernel_sets.check_sc(self.irreps_in, ls, self.correlation)
+        except NotImplementedError:
+            return False
+        full = cg.symcon_plan(self._coupling, self._ls, self.correlation)
+        live = cg.symcon_plan(self._coupling, ls, self.correlation)
+        off = {}
+        for which, lst in (("full", self._ls), ("live", ls)):
+            o = 0
+            for l in lst:
+                off[(which, l)] = o
+                o += 2 * l + 1
+        to_full = {}
+        for l in ls:
+            for m in range(2 * l + 1):
+                to_full[off[("live", l)] + m] = off[("full", l)] + m
+        row_of = {key: r for r, key in enumerate(full.terms)}
+        self._live_rows = torch.tensor([row_of[(nu, cls, to_full[o])] for nu, cls, o in live.terms],
+                                       dtype=torch.long)
+        self._live = ls
+        self._live_sig = cg.fnv1a64(cg.sc_signature(self._coupling, ls, self.correlation))
+        return True
+
+    def _config(self, live: bool = False):
+        if live:
+            if self._live_cfg is None:
+                self._live_cfg = _lib.sc_config_by_sig(self._live_sig)
+            return self._live_cfg
         if self._cfg is None:
             self._cfg = _lib.sc_config_by_sig(self._sig)
         return self._cfg
@@ -195,30 +241,42 @@ class SymmetricContraction(torch.nn.Module):
             ws.append(self.contractions[f"{self.mul}x{ir}"].weights[str(nu)])
         return torch.cat(ws, dim=0)                     # [K_total, mul]
 
-    def coefficients(self) -> torch.Tensor:
+    def coefficients(self, live: bool = False) -> torch.Tensor:
         """(U_sym @ W)^T with the 1.6 %-dense U_sym applied as CSR on the GPU: [mul, coef_ld],
-        rows zero-padded from nterms to the kernels' coefficient stride (CPU: [mul, nterms])."""
-        if self.u_sym.is_cuda:
-            if getattr(self, "_u_csr", None) is None:
-                self._u_csr = ops.SparseRows(self.u_sym)
-            ld = self._table.ldc if self._table else self._config()[1]["coef_ld"]
-            return ops.symcon_coefficients(self.weight_matrix(), self._u_csr, ld)
-        return torch.matmul(self.u_sym, self.weight_matrix()).t().contiguous()
+        rows zero-padded from nterms to the kernels' coefficient stride (CPU: [mul, nterms]).
+        ``live``: the rows of the live outputs' terms only (``restrict_outputs``)."""
+        live = live and self._live is not None
+        def u_rows():
+            if not live:
+                return self.u_sym
+            return self.u_sym.index_select(0, self._live_rows.to(self.u_sym.device))
 
-    def forward(self, x: torch.Tensor, y: torch.Tensor = None) -> torch.Tensor:
+        if self.u_sym.is_cuda:
+            attr = "_live_u_csr" if live else "_u_csr"
+            if getattr(self, attr, None) is None:
+                setattr(self, attr, ops.SparseRows(u_rows()))      # built once
+            ld = self._table.ldc if self._table else self._config(live)[1]["coef_ld"]
+            return ops.symcon_coefficients(self.weight_matrix(), getattr(self, attr), ld)
+        return torch.matmul(u_rows(), self.weight_matrix()).t().contiguous()
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor = None, live: bool = False) -> torch.Tensor:
         """``x``: the node rows ``[N, Σ mul·(2l+1)]`` in e3nn mul-major order (the fast path
         used by ``EquivariantProductBlock``), or the reference's ``reshape_irreps`` output
         ``[N, mul, Σ(2l+1)]`` (``gnn/mace.py:171-175,316-332``; that layout is converted back
         to rows, one copy).  ``y`` is the reference's element attribute, unused in its
         non-element-dependent branch (``gnn/mace.py:261-275``); it must be None here.
-        Returns ``[N, Σ mul·(2l_out+1)]`` mul-major, as the reference's ``torch.cat``."""
+        Returns ``[N, Σ mul·(2l_out+1)]`` mul-major, as the reference's ``torch.cat``; with
+        ``live`` (and a live form prepared by ``restrict_outputs``) the live l only."""
         if y is not None:
             raise NotImplementedError("element-dependent symmetric contraction (y given) is not "
                                       "on the hot path: the model passes y=None (gnn/blocks.py:486)")
         if x.dim() == 3:
             x = unreshape_irreps(self.irreps_in, x)
+        live = live and self._live is not None
+        ahead, self._ahead = self._ahead, None
+        if ahead is not None and ahead[3] != live:
+            ahead = None
         if self._table is not None:
-            ahead, self._ahead = self._ahead, None
             if ahead is not None:
                 coef = ahead[0]
                 torch.cuda.current_stream(x.device).wait_event(ahead[1])
@@ -226,35 +284,35 @@ class SymmetricContraction(torch.nn.Module):
             else:
                 coef = self.coefficients()
             return ops.symmetric_contraction_table(x, coef, self._table)
-        idx, info = self._config()
+        idx, info = self._config(live)
         side = ops.side_stream(x.device, 1) if (ops.OVERLAP and x.is_cuda) else None
         if side is None:
-            return ops.symmetric_contraction(x, self.coefficients(), idx, info, self.mul)
+            return ops.symmetric_contraction(x, self.coefficients(live), idx, info, self.mul)
         # the coefficient chain (weight matrix -> U_sym SpMM) runs on the side stream, so its
         # backward -- and the coefficient-gradient kernel launched there by the contraction's
         # backward -- overlaps the rest of the backward on the main stream
         main = torch.cuda.current_stream(x.device)
-        ahead, self._ahead = self._ahead, None
         if ahead is not None and ahead[2] is side:
             coef, ev = ahead[0], ahead[1]
             main.wait_event(ev)
         else:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                coef = self.coefficients()
+                coef = self.coefficients(live)
             main.wait_stream(side)
         coef.record_stream(main)
         return ops.symmetric_contraction(x, coef, idx, info, self.mul, side=side)
 
-    def coefficients_ahead(self, side) -> None:
+    def coefficients_ahead(self, side, live: bool = False) -> None:
         """Issue the coefficient chain (weight matrix -> U_sym SpMM) on the side stream now and
         keep (coef, event) for this module's next forward.  The model calls it for every layer
         at the start of its forward (the coefficients depend on the weights only), so each
         layer's main stream waits on work finished long before, instead of a main -> side ->
         main round trip at the layer (two cross-stream waits of ~20 us each on the critical
         path).  The caller orders ``side`` after the main stream's last weight update."""
+        live = live and self._live is not None
         with torch.cuda.stream(side):
-            coef = self.coefficients()
+            coef = self.coefficients(live)
         ev = torch.cuda.Event()
         ev.record(side)
-        self._ahead = (coef, ev, side)
+        self._ahead = (coef, ev, side, live)

@@ -46,6 +46,72 @@ RADIAL_AHEAD_OF_LAYER1 = os.environ.get("EELG_RADIAL_BEFORE_L1", "1") != "0"
 COEF_AHEAD = os.environ.get("EELG_COEF_AHEAD", "1") != "0"
 
 
+def _live_inputs(lin: Linear, live_out) -> tuple:
+    """the input slots of an ``o3.Linear`` that reach one of its output slots ``live_out``"""
+    return tuple(sorted({i for i, o in lin.instructions if o in set(live_out)}))
+
+
+def _merge_pieces(pieces):
+    """adjacent channel ranges of one slot joined"""
+    out = []
+    for s, c0, cnt in sorted(pieces):
+        if out and out[-1][0] == s and out[-1][1] + out[-1][2] == c0:
+            out[-1] = (s, out[-1][1], out[-1][2] + cnt)
+        else:
+            out.append((s, c0, cnt))
+    return tuple(out)
+
+
+def readout_liveness(readout: GeneralNonLinearReadoutBlock, final: Linear) -> Dict[str, tuple]:
+    """Which parts of the readout can reach the output of ``final`` (the stiffness linear),
+    walked back through the module structure: an ``o3.Linear`` joins equal irreps only
+    (its ``instructions``), the Gate passes a scalar slot through and multiplies a gated slot
+    by its own gate scalars (so a gate is live exactly when its gated slot is), and the pool
+    in between is per column.  Returns the live slots / pieces per module:
+
+    * ``final_in``: slots of ``final.irreps_in`` (= the readout's output irreps);
+    * ``gate_scalars`` / ``gate_gated``: slots of the Gate's scalars / gated irreps;
+    * ``gate_out``: slots of the Gate's output irreps (= ``linear_2``'s input);
+    * ``lin1_out``: pieces (slot, first channel, channels) of ``linear_1.irreps_out``, whose
+      first slot merges the scalars and every gate;
+    * ``hidden``: slots of ``linear_1.irreps_in``, the last layer's output irreps."""
+    gate = readout.equivariant_nonlin
+    final_in = _live_inputs(final, range(len(final.irreps_out)))
+    gate_out = _live_inputs(readout.linear_2, final_in)
+    ns = len(gate.irreps_scalars)
+    gate_scalars = tuple(j for j in gate_out if j < ns)
+    gate_gated = tuple(j - ns for j in gate_out if j >= ns)
+    # the Gate's input row as atoms -- the scalar slots, one run of gates per gated slot (a
+    # gate per channel, in slot order), the gated slots -- and each atom's piece of linear_1's
+    # output irreps, which are those of the Gate's input with equal neighbours merged
+    gate_ir = [ir for mul, ir in gate.irreps_gates for _ in range(mul)]
+    atoms, g0 = [("s", j, mul, ir) for j, (mul, ir) in enumerate(gate.irreps_scalars)], 0
+    for b, (mul, _) in enumerate(gate.irreps_gated):
+        if len(set(gate_ir[g0: g0 + mul])) != 1:
+            raise ValueError(f"the gates {gate.irreps_gates} of gated slot {b} are of several irreps")
+        atoms.append(("g", b, mul, gate_ir[g0]))
+        g0 += mul
+    atoms += [("x", b, mul, ir) for b, (mul, ir) in enumerate(gate.irreps_gated)]
+    where, s, c0, prev, last = {}, -1, 0, None, 0
+    for kind, idx, mul, ir in atoms:
+        if ir == prev:
+            c0 += last
+        else:
+            s, c0, prev = s + 1, 0, ir
+        where[(kind, idx)] = (s, c0, mul)
+        last = mul
+    lin1 = readout.linear_1
+    if s + 1 != len(lin1.irreps_out) or any(
+            sum(cnt for t, _, cnt in where.values() if t == k) != lin1.irreps_out[k].mul
+            for k in range(len(lin1.irreps_out))):
+        raise ValueError(f"{lin1.irreps_out} is not the simplified Gate input {gate.irreps_in}")
+    lin1_out = _merge_pieces([where[("s", j)] for j in gate_scalars]
+                             + [where[(k, b)] for k in "gx" for b in gate_gated])
+    hidden = _live_inputs(lin1, {p[0] for p in lin1_out})
+    return dict(final_in=final_in, gate_out=gate_out, gate_scalars=gate_scalars,
+                gate_gated=gate_gated, lin1_out=lin1_out, hidden=hidden)
+
+
 class GNN_Head(torch.nn.Module):  # noqa: N801
     def __init__(self, params: Namespace) -> None:
         super().__init__()
@@ -77,6 +143,42 @@ class GNN_Head(torch.nn.Module):  # noqa: N801
         self.sph_to_cart = Spherical_to_Cartesian()
         self.cart_to_Mandel = Cart_4_to_Mandel()
         self.positive_layer = PositiveLayer(params)
+        # forward returns nothing but the stiffness: the irreps of the last layer's output that
+        # cannot reach self.linear are not computed (ops.LIVE_OUT, EELG_LIVE_OUT=0: all are)
+        live = readout_liveness(self.nonlin_readout, self.linear)
+        self.live_irreps = Irreps([hidden[i] for i in live["hidden"]])
+        self.live_pruned = bool(ops.LIVE_OUT) and self._prune(live)
+
+    def _prune(self, live) -> bool:
+        """Restrict the last layer's contraction and product linear and the readout to the
+        live irreps.  False, with nothing changed: everything is live, or the live-output
+        contraction set does not exist (correlation 4, a list that was not generated)."""
+        ro, prod = self.nonlin_readout, self.layers[-1].product
+        lin1, gate, lin2 = ro.linear_1, ro.equivariant_nonlin, ro.linear_2
+        if live["hidden"] == tuple(range(len(lin1.irreps_in))):
+            return False
+        sc_slots = _live_inputs(prod.linear, live["hidden"])
+        ls = tuple(prod.linear.irreps_in[i].ir.l for i in sc_slots)
+        if [prod.linear.irreps_in[i] for i in sc_slots] != [
+                prod.symmetric_contractions.irreps_out[i] for i in sc_slots]:
+            return False
+        if (not prod.symmetric_contractions.restrict_outputs(ls)
+                or prod.symmetric_contractions._live is None):
+            return False
+
+        def whole(irreps, slots):
+            return tuple((s, 0, irreps[s].mul) for s in slots)
+
+        prod.linear.set_live(whole(prod.linear.irreps_in, sc_slots),
+                             whole(prod.linear.irreps_out, live["hidden"]))
+        lin1.set_live(whole(lin1.irreps_in, live["hidden"]), live["lin1_out"])
+        gate.set_live(live["gate_scalars"], live["gate_gated"])
+        lin2.set_live(whole(lin2.irreps_in, live["gate_out"]), whole(lin2.irreps_out, live["final_in"]))
+        self.linear.set_live(whole(self.linear.irreps_in, live["final_in"]), None)
+        # the Gate's compact input row is linear_1's compact output row, piece by piece
+        if lin1.live is None or gate.live is None or lin1.live._out_dim != gate.live.in_dim:
+            raise RuntimeError("live readout pieces do not line up")
+        return True
 
     def _radial_weights_ahead(self, edge_feats):
         """Every layer's radial MLP depends only on the edge features, so all of them run up
@@ -117,8 +219,9 @@ class GNN_Head(torch.nn.Module):  # noqa: N801
         main = torch.cuda.current_stream(device)
         side = ops.side_stream(device, 1)
         side.wait_stream(main)
-        for layer in self.layers:
-            layer.product.symmetric_contractions.coefficients_ahead(side)
+        for i, layer in enumerate(self.layers):
+            layer.product.symmetric_contractions.coefficients_ahead(
+                side, live=self.live_pruned and i == self.num_interactions - 1)
 
     def forward(self, edge_index, node_ft, edge_sh, edge_feats, batch_idx, num_graphs: int):
         csr, edge_sh, edge_feats = as_csr(edge_index, node_ft.shape[0], edge_sh, edge_feats)
@@ -128,7 +231,10 @@ class GNN_Head(torch.nn.Module):  # noqa: N801
         def run(i, h, residual=None):
             if evs[i] is not None:
                 torch.cuda.current_stream(h.device).wait_event(evs[i])
-            return self.layers[i](h, csr, edge_sh, edge_feats, tp_weights=ws[i], residual=residual)
+            # the last layer: only the irreps the readout can pass on to self.linear
+            live = self.live_pruned and i == self.num_interactions - 1
+            return self.layers[i](h, csr, edge_sh, edge_feats, tp_weights=ws[i], residual=residual,
+                                  live=live)
 
         node_ft = run(0, node_ft)
         if RADIAL_AHEAD_OF_LAYER1 and evs[-1] is not None:
@@ -138,9 +244,9 @@ class GNN_Head(torch.nn.Module):  # noqa: N801
             # node_ft + layer_i(node_ft) (gnn/model.py:95), the add fused into the layer's
             # last linear
             node_ft = run(i, node_ft, residual=node_ft)
-        out = self.nonlin_readout(node_ft)
+        out = self.nonlin_readout(node_ft, live=self.live_pruned)
         graph_ft = ops.graph_pool(out, batch_idx, num_graphs, self.global_reduction)
-        stiff = self.sph_to_cart(self.linear(graph_ft))
+        stiff = self.sph_to_cart(self.linear(graph_ft, live=self.live_pruned))
         return self.positive_layer(self.cart_to_Mandel(stiff))
 
 

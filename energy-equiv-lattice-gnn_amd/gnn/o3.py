@@ -98,6 +98,9 @@ class GradMailbox:
 
     def __init__(self):
         self.grad = None
+        # the deposited gradient's row layout: None = the residual's own rows, else the
+        # (slot, first channel, channels) pieces of the depositing linear's compact output
+        self.pieces = None
 
 
 class _IrrepsLinearFn(torch.autograd.Function):
@@ -115,11 +118,15 @@ class _IrrepsLinearFn(torch.autograd.Function):
         gy = gy.contiguous()
         gres = gy if ctx.needs_input_grad[5] else None      # y = linear(x) + residual
         if gres is not None and mb is not None:
-            mb.grad, gres = gres, None                      # added by the collecting linear
-        extra = None
+            # added by the collecting linear (compact rows: with the pieces they cover; the
+            # residual's other irreps get no gradient from here, an exact zero)
+            mb.grad, mb.pieces, gres = gres, (lin._out_pieces if lin._pruned else None), None
+        elif gres is not None and lin._pruned:
+            gres = lin._expand_out(gres)                    # autograd sums full residual rows
+        extra = pieces = None
         if mb is not None and not ctx.deposit:
-            extra, mb.grad = mb.grad, None
-        gx = lin._bwd_x(gy, weight, extra) if ctx.needs_input_grad[0] else None
+            extra, pieces, mb.grad, mb.pieces = mb.grad, mb.pieces, None, None
+        gx = lin._bwd_x(gy, weight, extra, pieces) if ctx.needs_input_grad[0] else None
         want_w, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if side is None or not (want_w or want_b):
             gw = lin._bwd_w(x, gy) if want_w else None
@@ -137,77 +144,84 @@ class _IrrepsLinearFn(torch.autograd.Function):
         return gx, gw, gb, None, None, gres, None
 
 
-class Linear(torch.nn.Module):
-    """e3nn ``o3.Linear`` on mul-major rows; HIP kernels (``eelg_linear_*``): forward and grad-x
-    on bf16 MFMA with fp32-accurate split operands where the irreps qualify
-    (``eelg_linear_fwd_pk``), fp32 MFMA otherwise and for grad-W."""
-
-    def __init__(self, irreps_in, irreps_out, internal_weights: bool = True,
-                 shared_weights: bool = True, biases: bool = False):
-        super().__init__()
-        self.irreps_in, self.irreps_out = Irreps(irreps_in), Irreps(irreps_out)
-        self.instructions: List[Tuple[int, int]] = [
-            (i, o) for i, (_, a) in enumerate(self.irreps_in)
-            for o, (_, b) in enumerate(self.irreps_out) if a == b]
-        fan = Counter()
-        for i, o in self.instructions:
-            fan[o] += self.irreps_in[i].mul
-        self.alpha = [1.0 / math.sqrt(fan[o]) for _, o in self.instructions]
-        self.weight_numel = sum(self.irreps_in[i].mul * self.irreps_out[o].mul
-                                for i, o in self.instructions)
-        self.weight = torch.nn.Parameter(torch.randn(self.weight_numel))
-        self.bias_slots = [o for o, (_, ir) in enumerate(self.irreps_out)
-                           if biases and ir.l == 0 and ir.p == 1]
-        nb = sum(self.irreps_out[o].mul for o in self.bias_slots)
-        if nb:
-            self.bias = torch.nn.Parameter(torch.zeros(nb))
-        else:
-            self.register_parameter("bias", None)
-        self._in_off, self._out_off = self.irreps_in.offsets(), self.irreps_out.offsets()
-        self._build_descriptors()
-        self._register_state_dict_hook(Linear._emit_derived)
-
-    def _covered(self):
-        # e3nn 0.5 masks by the weight instructions only (not the bias instructions)
-        return {o for _, o in self.instructions}
-
-    @staticmethod
-    def _emit_derived(module, state_dict, prefix, local_metadata):
-        ents = [("output_mask", _output_mask(module.irreps_out, module._covered()))]
-        if module.bias is None:
-            ents.append(("bias", torch.Tensor()))
-        _emit_e3nn_buffers(state_dict, prefix, ents)
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
-                              unexpected_keys, error_msgs):
-        _accept_output_mask(state_dict, prefix + "output_mask", self.irreps_out,
-                            self._covered(), error_msgs)
-        if self.bias is None:
-            _accept_empty(state_dict, prefix + "bias", error_msgs)
-        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
-                                      unexpected_keys, error_msgs)
-        self.invalidate_packed()
+class _LinearKernels:
+    """Descriptors and launches of an ``o3.Linear`` over given pieces of its rows: the
+    ``Linear`` module itself (every slot whole), and its live variant (``_LiveLinear``)."""
 
     def invalidate_packed(self) -> None:
         """forget the packed split weights (after a write the version counter does not see)"""
         if hasattr(self, "_pk_cache"):
             self._pk_cache.clear()
 
-    # -- descriptor tables for the C ABI (built once) ---------------------------
+    # -- live pieces ------------------------------------------------------------
+    @staticmethod
+    def full_pieces(irreps):
+        """the row layout as pieces (slot, first channel, channels): every slot, whole"""
+        return tuple((s, 0, mul) for s, (mul, _) in enumerate(irreps))
+
+    @staticmethod
+    def _piece_offsets(irreps, pieces):
+        """(offset of each piece in the compact row that holds exactly ``pieces``, row width)"""
+        offs, off = [], 0
+        for s, _, cnt in pieces:
+            offs.append(off)
+            off += cnt * irreps[s].ir.dim
+        return offs, off
+
+    def _set_pieces(self, in_pieces=None, out_pieces=None) -> None:
+        """The pieces of the input / output rows this object computes: ``(slot, first channel,
+        channels)`` in row order, None = every slot whole.  The input (output) rows are then
+        compact: exactly the listed pieces, ``[N, sum channels * (2l+1)]``.  Only the weight
+        entries joining a live input piece to a live output piece are read, and the gradient
+        of every other entry of ``weight`` / ``bias`` is an exact zero; parameter shapes and
+        layout do not change.  With both None this is the plain ``o3.Linear``."""
+        full_in, full_out = self.full_pieces(self.irreps_in), self.full_pieces(self.irreps_out)
+        self._in_pieces = full_in if in_pieces is None else tuple(tuple(p) for p in in_pieces)
+        self._out_pieces = full_out if out_pieces is None else tuple(tuple(p) for p in out_pieces)
+        for irreps, pieces in ((self.irreps_in, self._in_pieces), (self.irreps_out, self._out_pieces)):
+            if list(pieces) != sorted(pieces) or any(
+                    c0 < 0 or cnt <= 0 or c0 + cnt > irreps[s].mul for s, c0, cnt in pieces):
+                raise ValueError(f"live pieces {pieces} do not fit {irreps}")
+        self._pruned = self._in_pieces != full_in or self._out_pieces != full_out
+        self._in_poff, self._in_dim = self._piece_offsets(self.irreps_in, self._in_pieces)
+        self._out_poff, self._out_dim = self._piece_offsets(self.irreps_out, self._out_pieces)
+        self._build_descriptors()
+
+    def _expand_out(self, g: torch.Tensor) -> torch.Tensor:
+        """compact output rows -> full ``irreps_out`` rows, zeros elsewhere"""
+        full = g.new_zeros(g.shape[0], self.irreps_out.dim)
+        for (s, c0, cnt), off in zip(self._out_pieces, self._out_poff):
+            d = self.irreps_out[s].ir.dim
+            f0 = self._out_off[s] + c0 * d
+            full[:, f0: f0 + cnt * d] = g[:, off: off + cnt * d]
+        return full
+
+    # -- descriptor tables for the C ABI (built by _set_pieces) ------------------
     def _build_descriptors(self):
         from . import _lib
-        w_offs, off = [], 0
+        w_offs, off = {}, 0
         for i, o in self.instructions:
-            w_offs.append(off)
+            w_offs[(i, o)] = off
             off += self.irreps_in[i].mul * self.irreps_out[o].mul
-        self._w_offs = w_offs
+        self._w_offs = [w_offs[io] for io in self.instructions]
+        alpha = dict(zip(self.instructions, self.alpha))
         b_offs, boff = {}, 0
         for o in self.bias_slots:
             b_offs[o] = boff
             boff += self.irreps_out[o].mul
         self._b_offs = b_offs
+        ipc, opc = self._in_pieces, self._out_pieces
+        # the live (input piece, output piece) pairs: weight block of channels [a, a + ca) x
+        # [b, b + cb) of instruction (i, o), first entry w0, row stride mo
+        pairs = []
+        for pi, (i, a, ca) in enumerate(ipc):
+            for qi, (o, b, cb) in enumerate(opc):
+                if (i, o) in w_offs:
+                    mo = self.irreps_out[o].mul
+                    pairs.append((pi, qi, ca, cb, w_offs[(i, o)] + a * mo + b, mo, alpha[(i, o)]))
+        self._live_pairs = pairs
 
-        def slots(n_slots, dims, muls, offs, srcs, bias):
+        def slots(n_slots, dims, muls, offs, srcs, bias, roffs):
             if n_slots > _lib.LIN_MAXSLOT:
                 raise NotImplementedError("too many irreps slots for eelg_linear")
             desc = _lib.LinDesc()
@@ -218,6 +232,7 @@ class Linear(torch.nn.Module):
                 sl = desc.slot[s]
                 sl.y_off, sl.n_out, sl.d = offs[s], muls[s], dims[s]
                 sl.bias_off = bias.get(s, -1)
+                sl.r_off = roffs[s]
                 if len(srcs[s]) > _lib.LIN_MAXSRC:
                     raise NotImplementedError("too many sources for one irreps slot")
                 sl.n_src = len(srcs[s])
@@ -226,34 +241,63 @@ class Linear(torch.nn.Module):
                     sl.src[t].ldk, sl.src[t].ldj, sl.src[t].alpha = ldk, ldj, a
             return desc, self_max_d
 
-        out_srcs = [[] for _ in self.irreps_out]
-        in_srcs = [[] for _ in self.irreps_in]
-        for (i, o), wo, a in zip(self.instructions, w_offs, self.alpha):
-            mi, mo = self.irreps_in[i].mul, self.irreps_out[o].mul
-            out_srcs[o].append((self._in_off[i], mi, wo, mo, 1, a))
-            in_srcs[i].append((self._out_off[o], mo, wo, 1, mo, a))
+        out_srcs = [[] for _ in opc]
+        in_srcs = [[] for _ in ipc]
+        for pi, qi, ca, cb, w0, mo, a in pairs:
+            out_srcs[qi].append((self._in_poff[pi], ca, w0, mo, 1, a))
+            in_srcs[pi].append((self._out_poff[qi], cb, w0, 1, mo, a))
+        # a residual operand has the full irreps_out rows: each output piece's place in them
+        res_off = [self._out_off[o] + b * self.irreps_out[o].ir.dim for o, b, _ in opc]
         self._fwd_desc, self._fwd_maxd = slots(
-            len(self.irreps_out), [ir.dim for _, ir in self.irreps_out],
-            [m for m, _ in self.irreps_out], self._out_off, out_srcs, b_offs)
+            len(opc), [self.irreps_out[o].ir.dim for o, _, _ in opc], [cb for _, _, cb in opc],
+            self._out_poff, out_srcs,
+            {qi: b_offs[o] + b for qi, (o, b, _) in enumerate(opc) if o in b_offs}, res_off)
+        if self._out_pieces != self.full_pieces(self.irreps_out):
+            self._fwd_desc.res_row = self.irreps_out.dim
         self._bx_desc, self._bx_maxd = slots(
-            len(self.irreps_in), [ir.dim for _, ir in self.irreps_in],
-            [m for m, _ in self.irreps_in], self._in_off, in_srcs, {})
-        if len(self.instructions) > _lib.LINW_MAXINS:
+            len(ipc), [self.irreps_in[i].ir.dim for i, _, _ in ipc], [ca for _, _, ca in ipc],
+            self._in_poff, in_srcs, {}, [0] * len(ipc))
+        self._bx_res = {}
+        if len(pairs) > _lib.LINW_MAXINS:
             raise NotImplementedError("too many instructions for eelg_linear_bwd_w")
         wd = _lib.LinWDesc()
-        wd.n_ins = len(self.instructions)
-        wd.max_jt = max([(self.irreps_out[o].mul + 31) // 32 for _, o in self.instructions] or [1])
-        wd.max_ut = max([(self.irreps_in[i].mul + 31) // 32 for i, _ in self.instructions] or [1])
-        for t, ((i, o), wo, a) in enumerate(zip(self.instructions, w_offs, self.alpha)):
+        wd.n_ins = len(pairs)
+        wd.max_jt = max([(cb + 31) // 32 for _, _, _, cb, _, _, _ in pairs] or [1])
+        wd.max_ut = max([(ca + 31) // 32 for _, _, ca, _, _, _, _ in pairs] or [1])
+        for t, (pi, qi, ca, cb, w0, mo, a) in enumerate(pairs):
             e = wd.ins[t]
-            e.x_off, e.k, e.g_off = self._in_off[i], self.irreps_in[i].mul, self._out_off[o]
-            e.n_out, e.d, e.w_off, e.alpha = self.irreps_out[o].mul, self.irreps_in[i].ir.dim, wo, a
+            e.x_off, e.k, e.g_off = self._in_poff[pi], ca, self._out_poff[qi]
+            e.n_out, e.d, e.w_off, e.alpha = cb, self.irreps_in[ipc[pi][0]].ir.dim, w0, a
+            e.ldw = 0 if mo == cb else mo
         self._bw_desc = wd
         self._pk_ok = {"fwd": self._packable(self._fwd_desc), "bx": self._packable(self._bx_desc)}
         self._pk_cache = {}
-        self._bw_maxd = max([self.irreps_in[i].ir.dim for i, _ in self.instructions] or [1])
-        self._bw_tiles = sum(((self.irreps_in[i].mul + 31) // 32) * ((self.irreps_out[o].mul + 31) // 32)
-                             for i, o in self.instructions) or 1
+        self._bw_maxd = max([self.irreps_in[ipc[pi][0]].ir.dim for pi, *_ in pairs] or [1])
+        # the node slices of grad-W follow the whole linear's tile count, not the live pairs':
+        # each weight entry is then summed over the same slices whatever else is live
+        self._bw_slice_tiles = sum(((self.irreps_in[i].mul + 31) // 32) * ((self.irreps_out[o].mul + 31) // 32)
+                                   for i, o in self.instructions) or 1
+        # every weight entry is written by grad-W (else the partial sums start from zeros)
+        self._bw_covers = sum(ca * cb for _, _, ca, cb, _, _, _ in pairs) == self.weight_numel
+
+    def _bx_desc_with(self, pieces):
+        """the grad-x descriptor for an added gradient in compact rows of ``pieces`` (pieces of
+        this linear's input irreps): slots the pieces do not cover add nothing"""
+        from . import _lib
+        hit = self._bx_res.get(pieces)
+        if hit is not None:
+            return hit
+        offs, width = self._piece_offsets(self.irreps_in, pieces)
+        where = dict(zip(pieces, offs))
+        desc = _lib.LinDesc.from_buffer_copy(self._bx_desc)
+        desc.res_row = width
+        if set(pieces) - set(self._in_pieces):
+            raise NotImplementedError(f"added gradient pieces {pieces} are no input pieces "
+                                      f"{self._in_pieces} of this linear")
+        for s, pc in enumerate(self._in_pieces):
+            desc.slot[s].r_off = where.get(pc, -1)
+        self._bx_res[pieces] = (desc, width)
+        return desc, width
 
     @staticmethod
     def _packable(desc) -> bool:
@@ -296,7 +340,7 @@ class Linear(torch.nn.Module):
         from . import _lib
         if not (LIN_X6 and self._pk_ok[which] and x_row % 4 == 0 and out_row % 4 == 0
                 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
-                and (extra is None or extra.data_ptr() % 16 == 0)):
+                and (extra is None or (extra.data_ptr() % 16 == 0 and desc.res_row == 0))):
             return False
         pk = self._packed(which, weight.detach())
         _lib.check(_lib.load().eelg_linear_fwd_pk(
@@ -308,80 +352,170 @@ class Linear(torch.nn.Module):
     def _fwd(self, x, weight, bias, residual=None):
         from . import _lib
         n = x.shape[0]
-        y = torch.empty(n, self.irreps_out.dim, device=x.device, dtype=torch.float32)
+        y = torch.empty(n, self._out_dim, device=x.device, dtype=torch.float32)
         self._fwd_desc.max_rows = n * self._fwd_maxd
-        if residual is not None and (residual.shape != y.shape or residual.dtype != torch.float32
+        # (the residual has the full irreps_out rows, also when y holds the live pieces only)
+        want = (n, self.irreps_out.dim)
+        if residual is not None and (tuple(residual.shape) != want or residual.dtype != torch.float32
                                      or not residual.is_contiguous()):
             raise ValueError(f"residual {tuple(residual.shape)} {residual.dtype}: expected a "
-                             f"contiguous float32 {tuple(y.shape)}")
-        if self._run_pk("fwd", x, self.irreps_in.dim, weight, bias, residual, n, y,
-                        self.irreps_out.dim, self._fwd_desc):
+                             f"contiguous float32 {want}")
+        if self._run_pk("fwd", x, self._in_dim, weight, bias, residual, n, y,
+                        self._out_dim, self._fwd_desc):
             return y
         _lib.check(_lib.load().eelg_linear_fwd_res(
-            _lib.ptr(x), self.irreps_in.dim, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(residual), n,
-            _lib.ptr(y), self.irreps_out.dim, ctypes.byref(self._fwd_desc), _lib.stream(y)),
+            _lib.ptr(x), self._in_dim, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(residual), n,
+            _lib.ptr(y), self._out_dim, ctypes.byref(self._fwd_desc), _lib.stream(y)),
             "linear_fwd")
         return y
 
-    def _bwd_x(self, gy, weight, extra=None):
-        """grad-x; ``extra`` ([N, dim_in], e.g. a residual's gradient) is added in the epilogue"""
+    def _bwd_x(self, gy, weight, extra=None, extra_pieces=None):
+        """grad-x; ``extra`` (e.g. a residual's gradient) is added in the epilogue: rows of this
+        linear's input layout, or compact rows of ``extra_pieces`` (its other slots add zero)"""
         from . import _lib
         n = gy.shape[0]
-        gx = torch.empty(n, self.irreps_in.dim, device=gy.device, dtype=torch.float32)
-        self._bx_desc.max_rows = n * self._bx_maxd
+        gx = torch.empty(n, self._in_dim, device=gy.device, dtype=torch.float32)
+        desc, width = self._bx_desc, self._in_dim
+        if extra is not None and extra_pieces is not None and tuple(extra_pieces) != self._in_pieces:
+            desc, width = self._bx_desc_with(tuple(extra_pieces))
+        desc.max_rows = n * self._bx_maxd
         if extra is not None:
             extra = extra.contiguous()
-            if extra.shape != gx.shape or extra.dtype != torch.float32:
+            if tuple(extra.shape) != (n, width) or extra.dtype != torch.float32:
                 raise ValueError(f"linear grad-x: added gradient {tuple(extra.shape)} does not "
-                                 f"match {tuple(gx.shape)}")
-        if self._run_pk("bx", gy, self.irreps_out.dim, weight, None, extra, n, gx,
-                        self.irreps_in.dim, self._bx_desc):
+                                 f"match {(n, width)}")
+        if self._run_pk("bx", gy, self._out_dim, weight, None, extra, n, gx,
+                        self._in_dim, desc):
             return gx
         _lib.check(_lib.load().eelg_linear_fwd_res(
-            _lib.ptr(gy), self.irreps_out.dim, _lib.ptr(weight), None, _lib.ptr(extra), n,
-            _lib.ptr(gx), self.irreps_in.dim, ctypes.byref(self._bx_desc), _lib.stream(gx)),
+            _lib.ptr(gy), self._out_dim, _lib.ptr(weight), None, _lib.ptr(extra), n,
+            _lib.ptr(gx), self._in_dim, ctypes.byref(desc), _lib.stream(gx)),
             "linear_bwd_x")
         return gx
 
     def _bwd_w(self, x, gy):
         from . import _lib, ops
         n = x.shape[0]
-        if not self.instructions:
-            return torch.zeros_like(self.weight)
+        if not self._live_pairs:
+            return torch.zeros(self.weight_numel, device=x.device, dtype=torch.float32)
         # ~LINW_WG workgroups in total: (node slices) x (32x32 weight tiles of all
         # instructions); each slice leaves one partial weight gradient that the sum reads back
-        slices = max(1, min((n + 31) // 32, -(-LINW_WG // self._bw_tiles), LINW_MAX_SLICES))
+        slices = max(1, min((n + 31) // 32, -(-LINW_WG // self._bw_slice_tiles), LINW_MAX_SLICES))
         nps = -(-n // slices)
         slices = -(-n // nps)
         self._bw_desc.max_rows = n * self._bw_maxd
-        part = torch.empty(slices, self.weight_numel, device=x.device, dtype=torch.float32)
+        # (a pruned linear writes the live weight entries only: the others sum exact zeros)
+        part = (torch.empty if self._bw_covers else torch.zeros)(
+            slices, self.weight_numel, device=x.device, dtype=torch.float32)
         _lib.check(_lib.load().eelg_linear_bwd_w(
-            _lib.ptr(x), self.irreps_in.dim, _lib.ptr(gy), self.irreps_out.dim, n, nps,
+            _lib.ptr(x), self._in_dim, _lib.ptr(gy), self._out_dim, n, nps,
             _lib.ptr(part), slices, self.weight_numel, ctypes.byref(self._bw_desc), _lib.stream(part)),
             "linear_bwd_w")
         return ops.sum_rows(part)
 
     def _bwd_bias(self, gy):
         from . import ops
-        out = torch.empty(sum(self.irreps_out[o].mul for o in self.bias_slots), device=gy.device,
-                          dtype=torch.float32)
-        k = 0
-        for o in self.bias_slots:
-            m = self.irreps_out[o].mul
-            ops.sum_rows(gy[:, self._out_off[o]: self._out_off[o] + m], out=out[k: k + m])
-            k += m
+        nb = sum(self.irreps_out[o].mul for o in self.bias_slots)
+        live = [(self._b_offs[o] + b, off, cnt) for (o, b, cnt), off in zip(self._out_pieces, self._out_poff)
+                if o in self._b_offs]
+        out = (torch.empty if sum(c for _, _, c in live) == nb else torch.zeros)(
+            nb, device=gy.device, dtype=torch.float32)
+        for k, off, cnt in live:
+            ops.sum_rows(gy[:, off: off + cnt], out=out[k: k + cnt])
         return out
 
+
+class _LiveLinear(_LinearKernels):
+    """A ``Linear`` restricted to pieces of its rows (``Linear.set_live``): its own descriptors
+    over compact rows, the module's parameters."""
+
+    def __init__(self, lin: "Linear", in_pieces, out_pieces):
+        for k in ("irreps_in", "irreps_out", "instructions", "alpha", "weight_numel", "bias_slots",
+                  "_in_off", "_out_off"):
+            setattr(self, k, getattr(lin, k))
+        self._set_pieces(in_pieces, out_pieces)
+
+
+class Linear(_LinearKernels, torch.nn.Module):
+    """e3nn ``o3.Linear`` on mul-major rows; HIP kernels (``eelg_linear_*``): forward and grad-x
+    on bf16 MFMA with fp32-accurate split operands where the irreps qualify
+    (``eelg_linear_fwd_pk``), fp32 MFMA otherwise and for grad-W."""
+
+    def __init__(self, irreps_in, irreps_out, internal_weights: bool = True,
+                 shared_weights: bool = True, biases: bool = False):
+        super().__init__()
+        self.irreps_in, self.irreps_out = Irreps(irreps_in), Irreps(irreps_out)
+        self.instructions: List[Tuple[int, int]] = [
+            (i, o) for i, (_, a) in enumerate(self.irreps_in)
+            for o, (_, b) in enumerate(self.irreps_out) if a == b]
+        fan = Counter()
+        for i, o in self.instructions:
+            fan[o] += self.irreps_in[i].mul
+        self.alpha = [1.0 / math.sqrt(fan[o]) for _, o in self.instructions]
+        self.weight_numel = sum(self.irreps_in[i].mul * self.irreps_out[o].mul
+                                for i, o in self.instructions)
+        self.weight = torch.nn.Parameter(torch.randn(self.weight_numel))
+        self.bias_slots = [o for o, (_, ir) in enumerate(self.irreps_out)
+                           if biases and ir.l == 0 and ir.p == 1]
+        nb = sum(self.irreps_out[o].mul for o in self.bias_slots)
+        if nb:
+            self.bias = torch.nn.Parameter(torch.zeros(nb))
+        else:
+            self.register_parameter("bias", None)
+        self._in_off, self._out_off = self.irreps_in.offsets(), self.irreps_out.offsets()
+        self._set_pieces(None, None)
+        self.live = None             # the variant over live pieces (set_live), used on request
+        self._register_state_dict_hook(Linear._emit_derived)
+
+    def _covered(self):
+        # e3nn 0.5 masks by the weight instructions only (not the bias instructions)
+        return {o for _, o in self.instructions}
+
+    @staticmethod
+    def _emit_derived(module, state_dict, prefix, local_metadata):
+        ents = [("output_mask", _output_mask(module.irreps_out, module._covered()))]
+        if module.bias is None:
+            ents.append(("bias", torch.Tensor()))
+        _emit_e3nn_buffers(state_dict, prefix, ents)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
+                              unexpected_keys, error_msgs):
+        _accept_output_mask(state_dict, prefix + "output_mask", self.irreps_out,
+                            self._covered(), error_msgs)
+        if self.bias is None:
+            _accept_empty(state_dict, prefix + "bias", error_msgs)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
+                                      unexpected_keys, error_msgs)
+        self.invalidate_packed()
+
+    def invalidate_packed(self) -> None:
+        super().invalidate_packed()
+        if getattr(self, "live", None) is not None:
+            self.live.invalidate_packed()
+
+    def set_live(self, in_pieces=None, out_pieces=None) -> None:
+        """Prepare the variant that ``forward(..., live=True)`` runs: only the listed pieces
+        ``(slot, first channel, channels)`` of the input / output rows (None: all), compact
+        rows, exact zero gradients for the weight entries it does not read
+        (``_LinearKernels._set_pieces``).  A plain call computes everything as before."""
+        self.live = None
+        if in_pieces is not None or out_pieces is not None:
+            live = _LiveLinear(self, in_pieces, out_pieces)
+            self.live = live if live._pruned else None
+
+
     def forward(self, x: torch.Tensor, residual: torch.Tensor = None,
-                grad_mailbox: "GradMailbox" = None) -> torch.Tensor:
+                grad_mailbox: "GradMailbox" = None, live: bool = False) -> torch.Tensor:
         """``o3.Linear``; with ``residual`` returns ``linear(x) + residual`` with the add in the
         kernel epilogue (the layer residual of ``gnn/model.py:92-96``).  ``grad_mailbox``
         shared by the residual-adding linear and the first linear reading the residual moves
         the residual's gradient into that linear's grad-x epilogue (``GradMailbox``)."""
         from .ops import _f32, _require_device
         _require_device(x)
-        if x.shape[-1] != self.irreps_in.dim:
-            raise ValueError(f"Linear expects [..., {self.irreps_in.dim}], got {tuple(x.shape)}")
+        # live: the variant of set_live (compact rows of the live pieces) where one is set
+        k = self.live if (live and self.live is not None) else self
+        if x.shape[-1] != k._in_dim:
+            raise ValueError(f"Linear expects [..., {k._in_dim}], got {tuple(x.shape)}")
         from . import ops
         weight, bias = self.weight, self.bias
         side = None
@@ -394,20 +528,54 @@ class Linear(torch.nn.Module):
         if residual is not None:
             _require_device(residual)
             residual = _f32(residual)
-        return _IrrepsLinearFn.apply(_f32(x), weight, bias, self, side, residual, grad_mailbox)
+        return _IrrepsLinearFn.apply(_f32(x), weight, bias, k, side, residual, grad_mailbox)
+
+
+class _GatePlan:
+    """The slots a Gate pass runs over: ``scalars`` / ``gated`` slot indices (None: all).  Rows
+    are compact: the live scalars, the gates of the live gated slots (one per channel, in slot
+    order), the live gated slots."""
+
+    def __init__(self, gate: "Gate", scalars=None, gated=None):
+        ns, ng = len(gate.irreps_scalars), len(gate.irreps_gated)
+        self.scalars = tuple(range(ns)) if scalars is None else tuple(scalars)
+        self.gated = tuple(range(ng)) if gated is None else tuple(gated)
+        self.pruned = self.scalars != tuple(range(ns)) or self.gated != tuple(range(ng))
+        self.irreps_scalars = Irreps([tuple(gate.irreps_scalars[i]) for i in self.scalars])
+        self.irreps_gated = Irreps([tuple(gate.irreps_gated[i]) for i in self.gated])
+        self.n_gates = self.irreps_gated.num_irreps
+        self.in_dim = self.irreps_scalars.dim + self.n_gates + self.irreps_gated.dim
+        self.out_dim = self.irreps_scalars.dim + self.irreps_gated.dim
+        self.cst = gate.cst
+        self._gdesc = None
+
+    def desc(self):
+        from . import _lib
+        if self._gdesc is None:
+            d = _lib.GateDesc()
+            d.n_scal, d.n_gates, d.n_blk = self.irreps_scalars.dim, self.n_gates, len(self.irreps_gated)
+            for b, (mul, ir) in enumerate(self.irreps_gated):
+                d.blk_mul[b], d.blk_dim[b] = mul, ir.dim
+            self._gdesc = d
+        return self._gdesc
+
+    def fits_kernel(self) -> bool:
+        from . import _lib
+        return (len(self.irreps_gated) <= _lib.GATE_MAXBLK and self.irreps_gated.dim <= _lib.GATE_MAXGATED
+                and self.n_gates <= _lib.GATE_MAXGATES)
 
 
 class _GateFn(torch.autograd.Function):
     """e3nn ``nn.Gate`` as two fused HIP passes (``eelg_gate_fwd`` / ``eelg_gate_bwd``)."""
 
     @staticmethod
-    def forward(ctx, x, gate: "Gate"):
+    def forward(ctx, x, plan: _GatePlan):
         from . import _lib
-        y = torch.empty(x.shape[0], gate.irreps_out.dim, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_gate_fwd(_lib.ptr(x), x.shape[0], ctypes.byref(gate._desc()),
-                                             float(gate.cst), _lib.ptr(y), _lib.stream(y)), "gate_fwd")
+        y = torch.empty(x.shape[0], plan.out_dim, device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().eelg_gate_fwd(_lib.ptr(x), x.shape[0], ctypes.byref(plan.desc()),
+                                             float(plan.cst), _lib.ptr(y), _lib.stream(y)), "gate_fwd")
         ctx.save_for_backward(x)
-        ctx.gate = gate
+        ctx.plan = plan
         return y
 
     @staticmethod
@@ -417,7 +585,7 @@ class _GateFn(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.empty_like(x)
         _lib.check(_lib.load().eelg_gate_bwd(_lib.ptr(x), _lib.ptr(gy), x.shape[0],
-                                             ctypes.byref(ctx.gate._desc()), float(ctx.gate.cst),
+                                             ctypes.byref(ctx.plan.desc()), float(ctx.plan.cst),
                                              _lib.ptr(gx), _lib.stream(gx)), "gate_bwd")
         return gx, None
 
@@ -432,7 +600,16 @@ class Gate(torch.nn.Module):
         self.irreps_in = self.irreps_scalars + self.irreps_gates + self.irreps_gated
         self.irreps_out = self.irreps_scalars + self.irreps_gated
         self.cst = cg.silu_normalize2mom()
+        self._plan = _GatePlan(self)
+        self.live = None             # the plan over live slots (set_live), used on request
         self._register_state_dict_hook(Gate._emit_derived)
+
+    def set_live(self, scalars=None, gated=None) -> None:
+        """Prepare the pass that ``forward(x, live=True)`` runs: over the listed slots of
+        ``irreps_scalars`` and of ``irreps_gated`` (each gated slot with its gates) only, on
+        compact rows (``_GatePlan``).  A plain call computes everything as before."""
+        plan = _GatePlan(self, scalars, gated)
+        self.live = plan if plan.pruned else None
 
     # e3nn's Gate multiplies with an ElementwiseTensorProduct submodule ``mul`` (external
     # weights: an empty ``weight`` placeholder, and an output mask over the gated irreps)
@@ -452,36 +629,30 @@ class Gate(torch.nn.Module):
                                       unexpected_keys, error_msgs)
 
     def _desc(self):
-        from . import _lib
-        if getattr(self, "_gdesc", None) is None:
-            d = _lib.GateDesc()
-            d.n_scal, d.n_gates, d.n_blk = self.irreps_scalars.dim, self.irreps_gates.dim, len(self.irreps_gated)
-            for b, (mul, ir) in enumerate(self.irreps_gated):
-                d.blk_mul[b], d.blk_dim[b] = mul, ir.dim
-            self._gdesc = d
-        return self._gdesc
+        return self._plan.desc()
 
     def _fits_kernel(self) -> bool:
-        from . import _lib
-        return (len(self.irreps_gated) <= _lib.GATE_MAXBLK and self.irreps_gated.dim <= _lib.GATE_MAXGATED
-                and self.irreps_gates.dim <= _lib.GATE_MAXGATES)
+        return self._plan.fits_kernel()
 
-    def forward(self, x):
+    def forward(self, x, live: bool = False):
+        plan = self.live if (live and self.live is not None) else self._plan
+        if x.shape[-1] != plan.in_dim:
+            raise ValueError(f"Gate expects [..., {plan.in_dim}], got {tuple(x.shape)}")
         # the fused HIP passes cover gates up to the kernels' table sizes; wider readouts use
         # the torch form below (the readout tail is outside the HIP hot path)
-        if x.is_cuda and x.dtype == torch.float32 and GATE_FUSED and self._fits_kernel():
+        if x.is_cuda and x.dtype == torch.float32 and GATE_FUSED and plan.fits_kernel():
             from .ops import _f32
-            return _GateFn.apply(_f32(x), self)
+            return _GateFn.apply(_f32(x), plan)
         # one torch.split instead of per-block slices: its backward is a single cat, where
         # slice backwards would each zero-fill a full [n, dim_in] gradient and add it up
         # (six zero-fill + add pairs per gate; the values are identical either way)
-        gated = [mul * ir.dim for mul, ir in self.irreps_gated]
-        pieces = torch.split(x, [self.irreps_scalars.dim, self.irreps_gates.dim] + gated, dim=1)
+        gated = [mul * ir.dim for mul, ir in plan.irreps_gated]
+        pieces = torch.split(x, [plan.irreps_scalars.dim, plan.n_gates] + gated, dim=1)
         act = torch.nn.functional.silu
         scalars = self.cst * act(pieces[0])
-        gates = torch.split(self.cst * act(pieces[1]), [mul for mul, _ in self.irreps_gated], dim=1)
+        gates = torch.split(self.cst * act(pieces[1]), [mul for mul, _ in plan.irreps_gated], dim=1)
         out = [scalars]
-        for (mul, ir), blk, g in zip(self.irreps_gated, pieces[2:], gates):
+        for (mul, ir), blk, g in zip(plan.irreps_gated, pieces[2:], gates):
             out.append((blk.reshape(-1, mul, ir.dim) * g[:, :, None]).reshape(-1, mul * ir.dim))
         return torch.cat(out, dim=1)
 

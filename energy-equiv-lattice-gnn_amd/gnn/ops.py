@@ -53,6 +53,9 @@ TIMER = KernelTimer()
 # side-stream overlap of independent work (radial MLPs, symmetric-contraction coefficient
 # chain and its gradient); EELG_OVERLAP=0 runs everything in line on the current stream
 OVERLAP = os.environ.get("EELG_OVERLAP", "1") != "0"
+# GNN_Head: the last layer and the readout compute only the irreps the stiffness linear can
+# read (1), or everything as the reference does (0)
+LIVE_OUT = os.environ.get("EELG_LIVE_OUT", "1") != "0"
 SC_CMAJOR_ON_SIDE = os.environ.get("EELG_SC_CMAJOR_SIDE", "0") != "0"   # measured equal; fused keeps fewer bytes
 # the contraction's coefficient gradient on the coefficient side stream (1) or in line (0)
 SC_COEF_ON_SIDE = os.environ.get("EELG_SC_COEF_SIDE", "1") != "0"
@@ -715,8 +718,8 @@ class _SymCon(torch.autograd.Function):
         out = torch.empty(n, mul * info["Dout"], device=x.device, dtype=torch.float32)
         lib = _lib.load()
         tok = TIMER.start("sc_fwd")
-        _lib.check(lib.eelg_sc_fwd(cfg, _lib.ptr(x), _lib.ptr(coef), n, mul, _lib.ptr(out),
-                                   _lib.stream(out)), "sc_fwd")
+        _lib.check(lib.eelg_sc_fwd_rows(cfg, _lib.ptr(x), x.shape[1], _lib.ptr(coef), n, mul,
+                                        _lib.ptr(out), out.shape[1], _lib.stream(out)), "sc_fwd")
         TIMER.stop(tok)
         ctx.save_for_backward(x, coef)
         ctx.cfg, ctx.info, ctx.mul, ctx.side = cfg, info, mul, side
@@ -727,6 +730,8 @@ class _SymCon(torch.autograd.Function):
         x, coef = ctx.saved_tensors
         g = _a16(g)
         n = x.shape[0]
+        if g.shape[1] != ctx.mul * ctx.info["Dout"]:
+            raise ValueError(f"grad_out {tuple(g.shape)} vs mul {ctx.mul}, {ctx.info}")
         lib = _lib.load()
         gx = gcoef = None
         want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -753,10 +758,10 @@ class _SymCon(torch.autograd.Function):
             gx = torch.empty_like(x)
             tok = TIMER.start("sc_bwd_x")
             fuse = want_c and not cm_side
-            _lib.check(lib.eelg_sc_bwd_x_cm(ctx.cfg, _lib.ptr(x), _lib.ptr(coef), _lib.ptr(g), n,
-                                            ctx.mul, _lib.ptr(gx),
-                                            _lib.ptr(xt) if fuse else None,
-                                            _lib.ptr(gt) if fuse else None, _lib.stream(gx)),
+            _lib.check(lib.eelg_sc_bwd_x_rows(ctx.cfg, _lib.ptr(x), x.shape[1], _lib.ptr(coef),
+                                              _lib.ptr(g), g.shape[1], n, ctx.mul, _lib.ptr(gx),
+                                              _lib.ptr(xt) if fuse else None,
+                                              _lib.ptr(gt) if fuse else None, _lib.stream(gx)),
                        "sc_bwd_x")
             TIMER.stop(tok)
         if want_c:

@@ -43,6 +43,19 @@ int eelg_tp_info(int cfg, int* info7, uint64_t* sig);
  * up to a multiple of 16, so every channel row starts on a 64-byte line) */
 int eelg_sc_find(const char* name);
 int eelg_sc_info(int cfg, int* info8, uint64_t* sig);
+/* The output l of a set, in row order: ls8 receives them, the count is returned (< 0: error).
+ * The full sets ("sc_l4_c3") write every l of the coupling, 0 .. lmax.  A live-output set
+ * ("sc_l4_c3_o024": l = 0, 2, 4) evaluates only the polynomial terms of the listed outputs,
+ * for a consumer that reads nothing else (the last layer in front of the stiffness head,
+ * Linear(readout, "2x0e+2x2e+1x4e"), gnn/model.py:82-86).  Its output and output-gradient rows
+ * are compact: [N, mul * sum(2l+1)] over the listed l only, mul-major per l block (l = 0, 2, 4
+ * at mul 32: 480 floats against the full set's 800); x, grad_x and the coefficient layout
+ * (its own nterms / coef_ld) are as for any set.  The config indices of the live-output sets
+ * follow the full sets'. */
+int eelg_sc_outputs(int cfg, int* ls8);
+/* The set with cfg's coupling and correlation whose outputs are exactly ls[0 .. n_ls)
+ * (its index; < 0: none was generated). */
+int eelg_sc_find_outputs(int cfg, const int* ls, int n_ls);
 
 /* Edge geometry + embeddings.
  * Replaces get_edge_vectors_and_lengths (gnn/mace.py:338-352),
@@ -244,6 +257,11 @@ int eelg_csr_spmm(const int* rowptr, const int* col, const float* val, int n_row
  * access); a misaligned pointer returns -2. */
 int eelg_sc_fwd(int cfg, const float* x, const float* coef, int n_nodes, int mul, float* out,
                 void* stream);
+/* eelg_sc_fwd with the caller's row widths stated: x_row must be mul * D and out_row
+ * mul * D_out of the set (a live-output set's rows are narrower than the full set's), else the
+ * call fails with -2 and launches nothing. */
+int eelg_sc_fwd_rows(int cfg, const float* x, int x_row, const float* coef, int n_nodes, int mul,
+                     float* out, int out_row, void* stream);
 int eelg_sc_bwd_x(int cfg, const float* x, const float* coef, const float* grad_out, int n_nodes,
                   int mul, float* grad_x, void* stream);
 /* eelg_sc_bwd_x that also writes the channel-major copies xt[(c*D + a)*N + n] of x and
@@ -251,6 +269,11 @@ int eelg_sc_bwd_x(int cfg, const float* x, const float* coef, const float* grad_
  * stages anyway, replacing two eelg_sc_cmajor passes; xt / gt may be NULL. */
 int eelg_sc_bwd_x_cm(int cfg, const float* x, const float* coef, const float* grad_out,
                      int n_nodes, int mul, float* grad_x, float* xt, float* gt, void* stream);
+/* eelg_sc_bwd_x_cm with the row widths of x / grad_x (x_row) and grad_out (grad_row) checked
+ * against the set as in eelg_sc_fwd_rows. */
+int eelg_sc_bwd_x_rows(int cfg, const float* x, int x_row, const float* coef, const float* grad_out,
+                       int grad_row, int n_nodes, int mul, float* grad_x, float* xt, float* gt,
+                       void* stream);
 /* Channel-major copy xt[(c*D + a)*N + n] of a mul-major row tensor (feeds sc_bwd_coef);
  * which = 0: input (coupling) layout, 1: output layout. */
 int eelg_sc_cmajor(int cfg, int which, const float* x, int n_nodes, int mul, float* xt,
@@ -301,11 +324,17 @@ int eelg_scg_bwd_coef(const eelg_scg_desc* d, const unsigned* terms, const int* 
 #define EELG_LIN_MAXSRC 4
 #define EELG_LIN_MAXSLOT 8
 typedef struct { int x_off, k, w_off, ldk, ldj; float alpha; } eelg_lin_src;
-typedef struct { int y_off, n_out, d, bias_off, n_src; eelg_lin_src src[EELG_LIN_MAXSRC]; } eelg_lin_slot;
-typedef struct { int n_slots, max_jt, max_rows, pad; eelg_lin_slot slot[EELG_LIN_MAXSLOT]; } eelg_lin_desc;
+typedef struct { int y_off, n_out, d, bias_off, n_src; eelg_lin_src src[EELG_LIN_MAXSRC]; int r_off; } eelg_lin_slot;
+/* res_row / r_off: the layout of the residual operand of eelg_linear_fwd_res / _pk.  res_row = 0:
+ * y's own (row stride y_row, slot offset y_off; r_off is ignored).  res_row > 0: rows of res_row
+ * floats in which the slot's block starts at r_off, or r_off < 0: this slot adds no residual
+ * (a compact y over some irreps of a wider residual row, or the reverse).  eelg_linear_fwd_pk
+ * takes res_row = 0 only. */
+typedef struct { int n_slots, max_jt, max_rows, res_row; eelg_lin_slot slot[EELG_LIN_MAXSLOT]; } eelg_lin_desc;
 int eelg_linear_fwd(const float* x, int x_row, const float* w, const float* bias, int n_nodes,
                     float* y, int y_row, const eelg_lin_desc* desc, void* stream);
-/* eelg_linear_fwd plus a residual res (y's layout, may be NULL) added in the epilogue:
+/* eelg_linear_fwd plus a residual res (y's layout, or desc->res_row / r_off; may be NULL)
+ * added in the epilogue:
  * y = linear(x) + res, the layer residual h + layer_i(h) of gnn/model.py:92-96 with the
  * product block's o3.Linear (gnn/blocks.py:486) producing layer_i(h). */
 int eelg_linear_fwd_res(const float* x, int x_row, const float* w, const float* bias,
@@ -330,7 +359,10 @@ int eelg_linear_fwd_pk(const float* x, int x_row, const void* pack, const float*
  * nodes_per_slice nodes (sum over p on the caller side; deterministic).
  * n_partial must be >= ceil(n_nodes / nodes_per_slice). */
 #define EELG_LINW_MAXINS 8
-typedef struct { int x_off, k, g_off, n_out, d, w_off; float alpha; } eelg_linw_ins;
+/* ldw: the row stride of the instruction's weight block in w, 0 = n_out (a dense [k, n_out]
+ * block).  ldw > n_out addresses n_out columns of a wider block (w_off = the first column):
+ * the live columns of a partly read output slot; the other entries of partial are not written. */
+typedef struct { int x_off, k, g_off, n_out, d, w_off; float alpha; int ldw; } eelg_linw_ins;
 typedef struct { int n_ins, max_jt, max_ut, max_rows; eelg_linw_ins ins[EELG_LINW_MAXINS]; } eelg_linw_desc;
 int eelg_linear_bwd_w(const float* x, int x_row, const float* g, int g_row, int n_nodes,
                       int nodes_per_slice, float* partial, int n_partial, int w_total,

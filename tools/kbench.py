@@ -175,37 +175,45 @@ def main():
     rec("segment_sum unfused (7360)", timeit_if("segment_sum unfused (7360)", lambda: ops.segment_sum_csr(m7360, csr.rowptr, n), args.reps),
         4 * (e * 7360 + n * 7360 + e))
     del m7360
-    sc = SymmetricContraction(hid, hid, 3).to(dev)
-    sidx, sinfo = sc._config()
-    coef = sc.coefficients().detach()
-    xs = torch.randn(n, 800, device=dev)
-    nt = sinfo["nterms"]
-    rec("sc_fwd", timeit_if("sc_fwd", lambda: ops.symmetric_contraction(xs, coef, sidx, sinfo, 32), args.reps),
-        4 * 2 * n * 800, 2 * n * 32 * (nt + 3250))
-    gs = torch.randn(n, 800, device=dev)
-    gx = torch.empty_like(xs)
+    # the full contraction set, then the live-output set of the last layer (l = 0, 2, 4)
+    for sfx, live in (("", None), (" live o024", (0, 2, 4))):
+        sc = SymmetricContraction(hid, hid, 3).to(dev)
+        if live is not None:
+            assert sc.restrict_outputs(live)
+        # (a plain call of the module is the full set: the live form is asked for)
+        sidx, sinfo = sc._config(live is not None)
+        assert (sinfo["Dout"], sinfo["nterms"]) == ((15, 4521) if live else (25, 7519)), sinfo
+        orow = 32 * sinfo["Dout"]
+        coef = sc.coefficients(live=live is not None).detach()
+        assert coef.shape == (32, sinfo["coef_ld"])
+        xs = torch.randn(n, 800, device=dev)
+        nt = sinfo["nterms"]
+        rec("sc_fwd" + sfx, timeit_if("sc_fwd" + sfx, lambda: ops.symmetric_contraction(xs, coef, sidx, sinfo, 32), args.reps),
+            4 * n * (800 + orow), 2 * n * 32 * (nt + 3250))
+        gs = torch.randn(n, orow, device=dev)
+        gx = torch.empty_like(xs)
 
-    def scbx():
-        ops._lib.check(lib.eelg_sc_bwd_x(sidx, ops._lib.ptr(xs), ops._lib.ptr(coef), ops._lib.ptr(gs), n,
-                                         32, ops._lib.ptr(gx), ops._lib.stream(x)), "bx")
-    rec("sc_bwd_x", timeit_if("sc_bwd_x", scbx, args.reps), 4 * 3 * n * 800, 2 * n * 32 * (nt + 2 * 3250))
-    xt = torch.empty(800, n, device=dev)
-    gt = torch.empty(800, n, device=dev)
+        def scbx():
+            ops._lib.check(lib.eelg_sc_bwd_x(sidx, ops._lib.ptr(xs), ops._lib.ptr(coef), ops._lib.ptr(gs), n,
+                                             32, ops._lib.ptr(gx), ops._lib.stream(x)), "bx")
+        rec("sc_bwd_x" + sfx, timeit_if("sc_bwd_x" + sfx, scbx, args.reps), 4 * n * (2 * 800 + orow), 2 * n * 32 * (nt + 2 * 3250))
+        xt = torch.empty(800, n, device=dev)
+        gt = torch.empty(orow, n, device=dev)
 
-    def cm():
-        ops._lib.check(lib.eelg_sc_cmajor(sidx, 0, ops._lib.ptr(xs), n, 32, ops._lib.ptr(xt),
-                                          ops._lib.stream(x)), "cm")
-    rec("sc_cmajor", timeit_if("sc_cmajor", cm, args.reps), 4 * 2 * n * 800)
-    cm()
-    ops._lib.check(lib.eelg_sc_cmajor(sidx, 1, ops._lib.ptr(gs), n, 32, ops._lib.ptr(gt), ops._lib.stream(x)), "cm")
-    chunk = sinfo["coef_chunk"]                                     # as gnn/ops.py
-    nch = int(lib.eelg_sc_bwd_coef_parts(sidx, n, 32))
-    part = torch.empty(nch, 32, sinfo["coef_ld"], device=dev)
+        def cm():
+            ops._lib.check(lib.eelg_sc_cmajor(sidx, 0, ops._lib.ptr(xs), n, 32, ops._lib.ptr(xt),
+                                              ops._lib.stream(x)), "cm")
+        rec("sc_cmajor" + sfx, timeit_if("sc_cmajor" + sfx, cm, args.reps), 4 * 2 * n * 800)
+        cm()
+        ops._lib.check(lib.eelg_sc_cmajor(sidx, 1, ops._lib.ptr(gs), n, 32, ops._lib.ptr(gt), ops._lib.stream(x)), "cm")
+        chunk = sinfo["coef_chunk"]                                     # as gnn/ops.py
+        nch = int(lib.eelg_sc_bwd_coef_parts(sidx, n, 32))
+        part = torch.empty(nch, 32, sinfo["coef_ld"], device=dev)
 
-    def scbc():
-        ops._lib.check(lib.eelg_sc_bwd_coef(sidx, ops._lib.ptr(xt), ops._lib.ptr(gt), n, 32, chunk,
-                                            ops._lib.ptr(part), ops._lib.stream(x)), "bc")
-    rec("sc_bwd_coef", timeit_if("sc_bwd_coef", scbc, args.reps), None, 2 * n * 32 * (nt + 3250))
+        def scbc():
+            ops._lib.check(lib.eelg_sc_bwd_coef(sidx, ops._lib.ptr(xt), ops._lib.ptr(gt), n, 32, chunk,
+                                                ops._lib.ptr(part), ops._lib.stream(x)), "bc")
+        rec("sc_bwd_coef" + sfx, timeit_if("sc_bwd_coef" + sfx, scbc, args.reps), None, 2 * n * 32 * (nt + 3250))
     for name, ii, oo in [("lin 800->400 (readout, 16 ch)", hid, "16x0e+16x1o+16x2e+16x3o+16x4e"),
                          ("lin 800->800", hid, hid),
                          ("lin 7360->800", "160x0e+256x1o+320x2e+320x3o+288x4e", hid)]:

@@ -3,6 +3,9 @@
 kernel whose name matches a regex, or its full listing.
 
   python tools/kernel_isa.py <regex> [--list] [--top N]
+
+Every translation unit of the library is searched, so the live-output contraction sets
+(``sc_fwd_sc_l4_c3_o024`` ...) match like the full ones.
 """
 import argparse
 import collections

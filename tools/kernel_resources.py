@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """VGPR / SGPR / LDS / spill usage of every kernel in gnn/libeelg.so (from the code-object
-metadata notes; no GPU needed).  usage: python tools/kernel_resources.py [regex]"""
+metadata notes; no GPU needed), every translation unit: the full contraction sets and the
+live-output ones (``sc_*_o024`` ...) alike.  usage: python tools/kernel_resources.py [regex]
+The names are the mangled ones (``_Z15sc_fwd_sc_l4_c3PKfS0_iPf``), so a set's name is followed
+by the ``P`` of its first pointer argument, not by the end of the string:
+``'sc_(fwd|bwd_x|bwd_coefs)_sc_l4_c3(_o024)?PK'`` lists a full set beside its live set and leaves
+out the mul-16 / mul-64 copies (``..._m16PK``)."""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
