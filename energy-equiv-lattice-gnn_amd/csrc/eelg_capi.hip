@@ -432,7 +432,8 @@ const eelg_tp_cfg* eelg_tp_table(int* n) {
   // the per-mul tables concatenated once (thread-safe static initialisation)
   static const std::vector<eelg_tp_cfg> all = [] {
     std::vector<eelg_tp_cfg> v;
-    for (auto get : {eelg_tp_table_m32, eelg_tp_table_m16, eelg_tp_table_m64}) {
+    for (auto get : {eelg_tp_table_m32, eelg_tp_table_m16, eelg_tp_table_m64,
+                     eelg_tp_hid_table_m32, eelg_tp_hid_table_m16, eelg_tp_hid_table_m64}) {
       int k = 0;
       const eelg_tp_cfg* t = get(&k);
       v.insert(v.end(), t, t + k);

@@ -19,6 +19,8 @@ struct eelg_tp_sh_cfg {
 };
 
 #include "generated/eelg_gen_geom.hip"
+// the SH gradients of the further hidden l lists' sets (tpB_l4_h024, ...), a table of their own
+#include "generated/eelg_gen_geom_hid.hip"
 
 // ---------------------------------------------------------------------------
 // backward of edge_embed_kernel: one thread per edge
@@ -70,6 +72,8 @@ __global__ __launch_bounds__(256) void edge_embed_bwd_kernel(
 
 static const eelg_tp_sh_cfg* tp_sh_cfg(const char* name) {
   for (const eelg_tp_sh_cfg& c : kTpShConfigs)
+    if (strcmp(c.name, name) == 0) return &c;
+  for (const eelg_tp_sh_cfg& c : kTpShHidConfigs)
     if (strcmp(c.name, name) == 0) return &c;
   return nullptr;
 }

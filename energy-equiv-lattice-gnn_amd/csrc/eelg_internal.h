@@ -92,6 +92,11 @@ const eelg_tp_cfg* eelg_tp_table(int* n);
 const eelg_tp_cfg* eelg_tp_table_m16(int* n);
 const eelg_tp_cfg* eelg_tp_table_m32(int* n);
 const eelg_tp_cfg* eelg_tp_table_m64(int* n);
+// the sets of the further hidden l lists (generated/eelg_gen_hid_m*.hip: tpB_l4_h024, ...);
+// eelg_tp_table appends them after every table above, so the earlier config indices stand
+const eelg_tp_cfg* eelg_tp_hid_table_m16(int* n);
+const eelg_tp_cfg* eelg_tp_hid_table_m32(int* n);
+const eelg_tp_cfg* eelg_tp_hid_table_m64(int* n);
 
 // error reporting shared by the translation units of libeelg.so (eelg_capi.hip)
 int eelg_fail(int code, const char* fmt, ...);

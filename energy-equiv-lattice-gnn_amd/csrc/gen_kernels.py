@@ -190,6 +190,19 @@ def tp_configs() -> Dict[str, Tuple[Irreps, Irreps, Irreps]]:
     return out
 
 
+def tp_hidden_configs() -> Dict[str, Tuple[Irreps, Irreps, Irreps]]:
+    """The further hidden l lists of kernel_sets.HIDDEN_LS (the even one: ``tpB_l4_h024``) x
+    SH(lmax) -> the same interaction irreps.  They go to their own translation units
+    (generated/eelg_gen_hid*.hip, eelg_gen_geom_hid.hip), so the text of the sets above does
+    not change."""
+    out = {}
+    for name, lmax, ls in kernel_sets.tp_hidden_sets():
+        sh = Irreps.spherical_harmonics(lmax)
+        target = (sh * MUL).sort()[0].simplify()
+        out[name] = (Irreps(kernel_sets.hidden_irreps_str(lmax, MUL, ls)), sh, target)
+    return out
+
+
 def sc_configs() -> Dict[str, Tuple[str, Tuple[int, ...], int]]:
     """coupling = the interaction irreps (SH lmax), outputs = the hidden irreps, correlation
     1..3 (gnn/kernel_sets.py).  Hidden irreps beyond the SH lmax are not generated: the
@@ -898,9 +911,11 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
     return L
 
 
-def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32") -> Tuple[str, dict]:
+def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32",
+            with_bwf: bool = True) -> Tuple[str, dict]:
     """``wt`` = "f32" | "bf16": storage type of the edge-sized tensors (TP weights w and
-    grad_w, per-edge grad gxe); arithmetic is fp32 either way (BASELINE config 5)."""
+    grad_w, per-edge grad gxe); arithmetic is fp32 either way (BASELINE config 5).
+    ``with_bwf`` = False: no fused output-linear backward (``tp_bwf``) for this set."""
     bf = wt == "bf16"
     sfx = "_bw" if bf else ""
     WT = "unsigned short" if bf else "float"
@@ -1173,7 +1188,7 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
     L.append("  }")
     L.append("}")
     # fused output-linear grad-x + backward (mul 32: one channel group of 32 lanes)
-    bwf = CG == 1 and LW == 32
+    bwf = with_bwf and CG == 1 and LW == 32
     if bwf:
         L += _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf, ld_w, st_w)
     info = dict(din=din, dmid=dmid, wn=wn, nsh=nsh, ngroups=len(groups) * CG, nbgroups=len(bgroups) * CG,
@@ -2605,6 +2620,26 @@ def _sc_table_row(name: str, i: dict, outputs: bool = False) -> str:
             f'{"sc_bwd_coefs_" + name if i["cstream"] else "nullptr"}, {i["csets"]}{tail}}},')
 
 
+def _tp_table_row(name: str, i: dict, bf: bool) -> str:
+    """one eelg_tp_cfg initialiser; ``bf``: the set has the bf16-storage kernels (``_bw``)"""
+    lmax = int(name.split("_l")[1].split("_")[0])
+    bfk = (f"tp_fwd_{name}_bw, tp_bwd_{name}_bw, tp_bws_{name}, tp_bws_{name}_bw" if bf
+           else f"nullptr, nullptr, tp_bws_{name}, nullptr")
+    bwk = (f"tp_bwf_{name}, " + (f"tp_bwf_{name}_bw" if bf else "nullptr")) if i["bwf"] else "nullptr, nullptr"
+    bws_ = f"bwf_slots_{name}, bwf_alpha_{name}" if i["bwf"] else "nullptr, nullptr"
+    return (f'  {{"{name}", {i["din"]}, {i["dmid"]}, {i["wn"]}, {i["nsh"]}, {i["ngroups"]}, '
+            f'{i["npaths"]}, {lmax}, {i["nbgroups"]}, {i["nph"]}, {i["beph"]}, {i["fwpb"]}, 0x{i["sig"]:016x}ULL, tp_fwd_{name}, tp_bwd_{name}, '
+            f'{bfk}, {i["ngroups_bf"]}, {i["bxcd"]}, {bwk}, {i["bwf_r"]}, {i["tdim"]}, {bws_}}},')
+
+
+def _tp_pad_decl(configs) -> str:
+    """the row a tp_fwd stream reads for an edge past its range (also when the batch has no
+    edges and the edge tensors are empty): as long as the longest x / SH / weight row"""
+    pad = max(max(node.dim, (sh.dim + 3) // 4 * 4, sum(p.mul for p in cg.tp_paths(node, sh, target)))
+              for node, sh, target in configs.values())
+    return f"static __device__ __attribute__((aligned(16))) float eelg_tp_pad[{(pad + 3) // 4 * 4}];\n"
+
+
 def _write_if_changed(path: str, src: str) -> None:
     old = open(path).read() if os.path.exists(path) else None
     if old != src:
@@ -2658,6 +2693,7 @@ def main(outdir: str) -> None:
             "typedef float eelg_f2u __attribute__((ext_vector_type(2), aligned(4)));", ""]
     geom += [emit_sh_bwd(lmax) for lmax in kernel_sets.LMAX]
     geom_table = []
+    geom_hid, geom_hid_table = [], []
     global MUL
     for mul in kernel_sets.MULS:
         MUL = mul
@@ -2670,11 +2706,7 @@ def main(outdir: str) -> None:
         if mul == 32:
             for lmax in kernel_sets.LMAX:
                 parts.append(emit_sh(lmax))
-        # the row a tp_fwd stream reads for an edge past its range (also when the batch has no
-        # edges and the edge tensors are empty): as long as the longest x / SH / weight row
-        pad = max(max(node.dim, (sh.dim + 3) // 4 * 4, sum(p.mul for p in cg.tp_paths(node, sh, target)))
-                  for node, sh, target in tp_configs().values())
-        parts.append(f"static __device__ __attribute__((aligned(16))) float eelg_tp_pad[{(pad + 3) // 4 * 4}];\n")
+        parts.append(_tp_pad_decl(tp_configs()))
         tp_table, sc_table = [], []
         # bf16 storage of the edge tensors (BASELINE config 5) is generated for mul = 32 only
         bf = mul == 32
@@ -2694,15 +2726,7 @@ def main(outdir: str) -> None:
         # launch tables
         parts.append("\n// ===== config tables =====")
         parts.append(f"static const eelg_tp_cfg kTpConfigs[] = {{")
-        for name, i in tp_table:
-            lmax = int(name.split("_l")[1].split("_")[0])
-            bfk = (f"tp_fwd_{name}_bw, tp_bwd_{name}_bw, tp_bws_{name}, tp_bws_{name}_bw" if bf
-                   else f"nullptr, nullptr, tp_bws_{name}, nullptr")
-            bwk = (f"tp_bwf_{name}, " + (f"tp_bwf_{name}_bw" if bf else "nullptr")) if i["bwf"] else "nullptr, nullptr"
-            bws_ = f"bwf_slots_{name}, bwf_alpha_{name}" if i["bwf"] else "nullptr, nullptr"
-            parts.append(f'  {{"{name}", {i["din"]}, {i["dmid"]}, {i["wn"]}, {i["nsh"]}, {i["ngroups"]}, '
-                         f'{i["npaths"]}, {lmax}, {i["nbgroups"]}, {i["nph"]}, {i["beph"]}, {i["fwpb"]}, 0x{i["sig"]:016x}ULL, tp_fwd_{name}, tp_bwd_{name}, '
-                         f'{bfk}, {i["ngroups_bf"]}, {i["bxcd"]}, {bwk}, {i["bwf_r"]}, {i["tdim"]}, {bws_}}},')
+        parts += [_tp_table_row(name, i, bf) for name, i in tp_table]
         parts.append("};")
         parts.append("static const eelg_sc_cfg kScConfigs[] = {")
         for name, i in sc_table:
@@ -2732,7 +2756,40 @@ def main(outdir: str) -> None:
         live.append("};")
         live.append(f"const eelg_sc_cfg* eelg_sc_live_table_m{mul}(int* n) {{ *n = (int)(sizeof(kScLiveConfigs)/sizeof(kScLiveConfigs[0])); return kScLiveConfigs; }}")
         _write_if_changed(os.path.join(outdir, f"eelg_gen_live_m{mul}.hip"), "\n".join(live) + "\n")
+        # the further hidden l lists' interaction sets of this channel count: their own
+        # translation unit with its own pad row and table (no tp_bwf: off by default, not widened)
+        hid_cfgs = tp_hidden_configs()
+        if hid_cfgs:
+            hid = list(header) + [_tp_pad_decl(hid_cfgs)]
+            hid_table = []
+            for name, (node, sh, target) in hid_cfgs.items():
+                code, nshp = emit_tp_bwd_sh(name + sfx, node, sh, target)
+                geom_hid.append(code)
+                geom_hid_table.append((name + sfx, nshp))
+                code, info = emit_tp(name + sfx, node, sh, target, with_bwf=False)
+                hid.append(code)
+                info["ngroups_bf"] = 0
+                if bf:
+                    code_bf, info_bf = emit_tp(name + sfx, node, sh, target, "bf16", with_bwf=False)
+                    hid.append(code_bf)
+                    info["ngroups_bf"] = info_bf["ngroups"]
+                hid_table.append((name + sfx, info))
+            hid.append("\n// ===== config table =====")
+            hid.append("static const eelg_tp_cfg kTpHidConfigs[] = {")
+            hid += [_tp_table_row(name, i, bf) for name, i in hid_table]
+            hid.append("};")
+            hid.append(f"const eelg_tp_cfg* eelg_tp_hid_table_m{mul}(int* n) {{ *n = (int)(sizeof(kTpHidConfigs)/sizeof(kTpHidConfigs[0])); return kTpHidConfigs; }}")
+            _write_if_changed(os.path.join(outdir, f"eelg_gen_hid_m{mul}.hip"), "\n".join(hid) + "\n")
     MUL = kernel_sets.MUL
+    if geom_hid_table:
+        # the SH gradients of those sets (included by eelg_geom.hip after eelg_gen_geom.hip, whose
+        # vector types they use)
+        geom_hid = (["// GENERATED by csrc/gen_kernels.py -- do not edit (included by eelg_geom.hip)", ""]
+                    + geom_hid + ["\n// ===== SH-gradient kernels by config name =====",
+                                  "static const eelg_tp_sh_cfg kTpShHidConfigs[] = {"]
+                    + [f'  {{"{name}", {nshp}, tp_bwd_sh_{name}}},' for name, nshp in geom_hid_table]
+                    + ["};"])
+        _write_if_changed(os.path.join(outdir, "eelg_gen_geom_hid.hip"), "\n".join(geom_hid) + "\n")
     geom.append("\n// ===== SH-gradient kernels by config name =====")
     geom.append("static const eelg_tp_sh_cfg kTpShConfigs[] = {")
     geom += [f'  {{"{name}", {nshp}, tp_bwd_sh_{name}}},' for name, nshp in geom_table]

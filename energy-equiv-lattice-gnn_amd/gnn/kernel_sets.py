@@ -6,8 +6,10 @@ the supported list, not at the first forward).
 Reference ``params`` space (``gnn/model.py:31-42``, ``gnn/mace.py:112-177``): ``lmax`` (SH),
 ``hidden_irreps``, ``correlation``.  Generated here:
 
-* tensor product: SH lmax 1..4, node irreps ``{mul}x0e`` (first layer) or the natural-parity
-  hidden irreps ``{mul}x0e+{mul}x1o+...`` up to the SH lmax (later layers);
+* tensor product: SH lmax 1..4, node irreps ``{mul}x0e`` (first layer) or one of the hidden
+  irreps of ``HIDDEN_LS`` (later layers): every natural-parity l up to the SH lmax
+  (``{mul}x0e+{mul}x1o+...``, sets ``tpB_l4``), or the even l only (``{mul}x0e+{mul}x2e+{mul}x4e``,
+  sets ``tpB_l4_h024``: all the stiffness head reads);
 * symmetric contraction: the same lmax, outputs = those hidden irreps, correlation 1..3
   generated; correlation 4 (the reference's ``filter_ir_mid`` coupling) runs the table-driven
   kernels (``csrc/eelg_scg.hip``) for SH lmax <= 3 (``TABLE_LMAX``: at lmax 4 the reference's
@@ -35,14 +37,46 @@ TABLE_LMAX = 3
 # from the last layer (``model.live_output_irreps`` derives them from the module structure;
 # these are the lists the generator builds, not a rule the model applies)
 LIVE_OUT = {1: (0,), 2: (0, 2), 3: (0, 2), 4: (0, 2, 4)}
+# the hidden l lists generated per SH lmax (``hidden_irreps`` = mul channels of each listed l,
+# natural parity): the full list first, then the even one (= LIVE_OUT[lmax]).  A further list
+# (say a hidden lmax below the SH lmax) is one more entry here: the set names, the generator
+# and the checks below follow this table.
+HIDDEN_LS = {
+    1: ((0, 1), (0,)),
+    2: ((0, 1, 2), (0, 2)),
+    3: ((0, 1, 2, 3), (0, 2)),
+    4: ((0, 1, 2, 3, 4), (0, 2, 4)),
+}
 
 
 def natural(l: int) -> str:
     return f"{l}{'e' if l % 2 == 0 else 'o'}"
 
 
-def hidden_irreps_str(lmax: int, mul: int = MUL) -> str:
-    return "+".join(f"{mul}x{natural(l)}" for l in range(lmax + 1))
+def hidden_irreps_str(lmax: int, mul: int = MUL, ls: Tuple[int, ...] = None) -> str:
+    """``mul`` channels of every l in ``ls`` (default: every l up to ``lmax``)"""
+    return "+".join(f"{mul}x{natural(l)}" for l in (range(lmax + 1) if ls is None else ls))
+
+
+def hidden_lists(lmax: int) -> Tuple[Tuple[int, ...], ...]:
+    """the hidden l lists generated for an SH lmax, the full one first"""
+    return HIDDEN_LS.get(lmax, ())
+
+
+def tp_set_name(lmax: int, ls: Tuple[int, ...] = None) -> str:
+    """the tensor-product set of hidden l list ``ls`` x SH(lmax): ``tpB_l4`` (every l up to
+    lmax), ``tpA_l4`` (scalars only: also the first layer's set) or ``tpB_l4_h024``"""
+    if ls is None or tuple(ls) == tuple(range(lmax + 1)):
+        return f"tpB_l{lmax}"
+    if tuple(ls) == (0,):
+        return f"tpA_l{lmax}"
+    return f"tpB_l{lmax}_h" + "".join(str(l) for l in ls)
+
+
+def tp_hidden_sets():
+    """(set name, SH lmax, hidden l list) of the sets beyond ``tpA_l*`` / ``tpB_l*``"""
+    return tuple((tp_set_name(lmax, ls), lmax, ls) for lmax in LMAX for ls in hidden_lists(lmax)[1:]
+                 if ls != (0,))
 
 
 def coupling_str(lmax: int) -> str:
@@ -58,16 +92,23 @@ def sc_set_name(lmax: int, corr: int, ls: Tuple[int, ...] = None) -> str:
 
 
 def sc_output_lists(lmax: int) -> Tuple[Tuple[int, ...], ...]:
-    """the output l lists generated for a coupling lmax: all of them, and the live subset"""
+    """the output l lists generated for a coupling lmax: all of them, the live subset, and the
+    hidden l lists of ``HIDDEN_LS`` (a product block's outputs are the hidden irreps; today the
+    even list is the live one), each once, the full list first"""
     full = tuple(range(lmax + 1))
-    live = LIVE_OUT.get(lmax)
-    return (full,) if live is None or live == full else (full, live)
+    out = [full]
+    for ls in (LIVE_OUT.get(lmax),) + tuple(hidden_lists(lmax)):
+        if ls is not None and ls not in out:
+            out.append(ls)
+    return tuple(out)
 
 
 def supported_text() -> str:
-    return (f"generated kernel sets: SH lmax in {LMAX} with hidden_irreps "
-            f"'{hidden_irreps_str(1)}' .. '{hidden_irreps_str(4)}' (mul channels of every l up to "
-            f"the SH lmax, mul in {MULS}), correlation in {CORRELATIONS}; correlation "
+    lists = "; ".join(f"lmax {k}: " + " or ".join(f"'{hidden_irreps_str(k, MUL, ls)}'" for ls in v)
+                      for k, v in HIDDEN_LS.items())
+    return (f"generated kernel sets: SH lmax in {LMAX} with hidden_irreps of equal channel counts "
+            f"(mul in {MULS}; shown for {MUL}) and one of the l lists {lists}; "
+            f"correlation in {CORRELATIONS}; correlation "
             f"{TABLE_CORRELATIONS[0]} (table-driven) for SH lmax <= {TABLE_LMAX}; contraction "
             f"outputs: every l up to the SH lmax, or (correlation in {CORRELATIONS}) the live "
             f"lists " + ", ".join(f"lmax {k}: l in {v}" for k, v in LIVE_OUT.items()))
@@ -85,7 +126,8 @@ def check_tp(node, sh, target) -> None:
     lmax = sh.lmax
     mul = mul_of(node)
     ok = (lmax in LMAX and mul in MULS and str(sh) == str(_sh(lmax))
-          and str(node) in (f"{mul}x0e", hidden_irreps_str(lmax, mul))
+          and str(node) in (f"{mul}x0e",) + tuple(hidden_irreps_str(lmax, mul, ls)
+                                                   for ls in hidden_lists(lmax))
           and str(target) == coupling_target(lmax, mul))
     if not ok:
         raise NotImplementedError(

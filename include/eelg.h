@@ -32,6 +32,12 @@ const char* eelg_last_error(void);
 
 /* Config discovery: the irreps-specialised kernels are looked up by name
  * ("tpA_l4" = 32x0e node irreps, "tpB_l4" = 32x0e+..+32x4e, "sc_l4_c3" ...).
+ * Even-parity hidden irreps have sets of their own, named by their l list: "tpB_l2_h02" and
+ * "tpB_l3_h02" (32x0e+32x2e x SH(2) / SH(3)) and "tpB_l4_h024" (32x0e+32x2e+32x4e x SH(4): 24
+ * paths, weight_numel 768, dmid 4288 against tpB_l4's 42 / 1344 / 7360), each also as "_m16" /
+ * "_m64".  Their config indices follow every earlier set's.  They serve every eelg_tp_* entry
+ * point below (bf16 storage at mul 32, as the other sets) and eelg_tp_bwd_sh, except the fused
+ * backward: eelg_tp_bwd_fused* and eelg_tp_bwf_slot return -2 for them.
  * info receives {din, dmid, weight_numel, nsh, ngroups, npaths, lmax};
  * sig is a structural hash the host re-derives to detect a stale build. */
 int eelg_tp_find(const char* name);
@@ -124,7 +130,7 @@ int eelg_tp_bwd_sender_bf16(int cfg, const float* x, const float* sh, const void
  * linear's grad-x followed by eelg_tp_bwd (gnn/blocks.py:591-604 autograd): grad_agg is computed
  * per receiver tile into LDS and never written to HBM.  Writes grad_w [E, wn] and the per-edge
  * grad_x rows gxe [E, din] in receiver-sorted edge order, as eelg_tp_bwd; rowptr is the receiver
- * CSR (int32 [n_nodes + 1]) and receiver the sorted edges' receivers (int32 [E]).  Generated for mul 32; returns -2 for other configs.  The linear
+ * CSR (int32 [n_nodes + 1]) and receiver the sorted edges' receivers (int32 [E]).  Generated for mul 32 (tpA_l*, tpB_l* only, not the "_h" sets); returns -2 for other configs.  The linear
  * is o3.Linear(irreps_mid.simplify(), target): eelg_tp_bwf_slot returns, per TP slot, the
  * weight offset of its 32 x 32 block, its alpha and its gy offset, for the caller to check
  * against its own linear before using this path. */

@@ -156,6 +156,41 @@ def main():
                        "tp_bwd_sh")
     sh_bytes = 4 * (n * 800 + e * info["wn"] + 2 * e + e * 28 + n * info["dmid"])
     rec("tp_bwd_sh (B)", timeit_if("tp_bwd_sh (B)", tpsh, args.reps), sh_bytes, tp_flops)
+    # the even hidden irreps' set (hidden 32x0e+32x2e+32x4e: 24 of the 42 paths) beside the full
+    # one, same graph and byte formulas (--only 'tp_(fwd|bwd|bwd_sh) \(' times both families)
+    hname = "tpB_l4_h024"
+    if want(f"tp_fwd ({hname})") or want(f"tp_bwd ({hname})") or want(f"tp_bwd_sh ({hname})"):
+        ehid = "32x0e+32x2e+32x4e"
+        hblk = TensorProductInteractionBlock(ehid, sh_ir, "12x0e", hid, 4.0).to(dev)
+        hidx, hinfo = hblk._config()
+        assert hidx == ops._lib.tp_config(hname)[0]
+        hd, hwn, hmid = hinfo["din"], hinfo["wn"], hinfo["dmid"]
+        hx = torch.randn(n, hd, device=dev)
+        hw = torch.randn(e, hwn, device=dev)
+        hagg = ops.tp_interaction(hx, sh, hw, csr, hidx, hinfo, 0.25)
+        rec(f"tp_fwd ({hname})",
+            timeit_if(f"tp_fwd ({hname})", lambda: ops.tp_interaction(hx, sh, hw, csr, hidx, hinfo, 0.25), args.reps),
+            4 * (n * hd + e * 25 + e * hwn + e + n + 1 + n * hmid))
+        hg = torch.randn_like(hagg)
+        hgw = torch.empty_like(hw)
+        hgxe = torch.empty(e, hd, device=dev)
+
+        def htpb():
+            ops._lib.check(lib.eelg_tp_bwd(hidx, ops._lib.ptr(hx), ops._lib.ptr(sh), ops._lib.ptr(hw),
+                                           ops._lib.ptr(csr.sender), ops._lib.ptr(csr.receiver), e,
+                                           ops._lib.ptr(hg), 0.25, ops._lib.ptr(hgw), ops._lib.ptr(hgxe),
+                                           ops._lib.stream(hx)), "tp_bwd")
+        rec(f"tp_bwd ({hname})", timeit_if(f"tp_bwd ({hname})", htpb, args.reps),
+            4 * (n * hd + e * 25 + 2 * e * hwn + 2 * e + e * hd + n * hmid))
+
+        def htpsh():
+            ops._lib.check(lib.eelg_tp_bwd_sh(hidx, ops._lib.ptr(hx), None, ops._lib.ptr(hw),
+                                              ops._lib.ptr(csr.sender), ops._lib.ptr(csr.receiver), e,
+                                              ops._lib.ptr(hg), 0.25, ops._lib.ptr(gsh), ops._lib.stream(hx)),
+                           "tp_bwd_sh")
+        rec(f"tp_bwd_sh ({hname})", timeit_if(f"tp_bwd_sh ({hname})", htpsh, args.reps),
+            4 * (n * hd + e * hwn + 2 * e + e * 28 + n * hmid))
+        del hx, hw, hagg, hg, hgw, hgxe
     # fused output-linear grad-x + TP backward (replaces lin 7360->800 bwd_x + tp_bwd)
     gyl = torch.randn(n, 800, device=dev)
     lw = blk.linear.weight.detach().contiguous()
