@@ -56,6 +56,10 @@ _SIGS = {
     "eelg_cgc_fwd_ef_res": ([_P] * 6 + [_P, _I, _I, _P, _P, _P], _I),
     "eelg_cgc_bwd_ef": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P], _I),
     "eelg_cgc_bwd_ef_parts": ([_I], _I),
+    "eelg_nnconv_fwd": ([_P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
+    "eelg_nnconv_bwd_edge": ([_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P], _I),
+    "eelg_nnconv_bwd_w_parts": ([_I, _I], _I),
+    "eelg_nnconv_bwd_w": ([_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P], _I),
     "eelg_csr_spmm": ([_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _P], _I),
     "eelg_sc_fwd": ([_I, _P, _P, _I, _I, _P, _P], _I),
     "eelg_sc_bwd_x": ([_I, _P, _P, _P, _I, _I, _P, _P], _I),
@@ -117,6 +121,7 @@ class LinWDesc(ctypes.Structure):
 RADIAL_MAXH = 3
 GATE_MAXBLK = 8
 CGC_MAXD = 256           # include/eelg.h EELG_CGC_MAXD
+NNC_WIDTHS = (32, 64)    # include/eelg.h: the built NNConv widths (EELG_NNC_MAXD 64)
 GATE_MAXGATED = 2048     # include/eelg.h EELG_GATE_MAXGATED / EELG_GATE_MAXGATES
 GATE_MAXGATES = 512
 

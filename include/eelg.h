@@ -247,6 +247,44 @@ int eelg_cgc_bwd_ef(const float* ps, const float* pr, const float* ef, const flo
 #define EELG_CGC_RPW 8
 int eelg_cgc_bwd_ef_parts(int n_nodes);
 
+/* Edge-conditioned convolution (NNConv benchmark model): replaces PyG's
+ *   weight = nn(edge_attr).view(-1, D, D); msg = matmul(x_j.unsqueeze(1), weight).squeeze(1)
+ *   (torch_geometric NNConv.message, as built by scripts/benchmark_models/nnconv_models.py:32-44
+ *   and called at :73) with nn's last Linear + ReLU folded in:
+ *   msg[e, o] = sum_i x[sender[e], i] relu(sum_k h[e, k] w3[i*D + o, k] + b3[i*D + o])
+ * h [E, D]: the output of nn's first two Linear + ReLU; w3 [D*D, D], b3 [D*D]: nn's last Linear.
+ * The [E, D*D] per-edge matrices exist only in MFMA accumulators (v_mfma_f32_32x32x2_f32, exact
+ * fp32 products).  Edges in the receiver-sorted order of the CSR; the aggr='add' receiver sum is
+ * eelg_segment_sum_csr(msg, rowptr).  Built for D in {32, 64}; -2 for another D or for a float
+ * pointer that is not 16-byte aligned (rows are read as float4).  n_edges == 0 launches nothing. */
+#define EELG_NNC_MAXD 64
+int eelg_nnconv_fwd(const float* x, const float* h, const float* w3, const float* b3,
+                    const int* sender, int n_edges, int D, float* msg, void* stream);
+/* Backward w.r.t. the per-edge operands, Z recomputed per tile, g = grad_agg[receiver[e]] ([N, D],
+ * the gradient of the receiver sums):
+ *   gxe[e, i]    = sum_o relu(Z)[e, i, o] g[e, o]       (grad x = eelg_segment_sum_csr(gxe, srowptr, sperm))
+ *   grad_h[e, k] = sum_{i, o} [Z > 0] x[sender[e], i] g[e, o] w3[i*D + o, k]
+ * (autograd's backward of the matmul, the view and nn's last ReLU + Linear in the reference). */
+int eelg_nnconv_bwd_edge(const float* x, const float* h, const float* w3, const float* b3,
+                         const int* sender, const int* receiver, int n_edges, int D,
+                         const float* grad_agg, float* gxe, float* grad_h, void* stream);
+/* Backward w.r.t. nn's last Linear: part [eelg_nnconv_bwd_w_parts(n_edges, D), D*D*(D+1)], each
+ * row = [grad w3 (D*D x D) | grad b3 (D*D)] over one contiguous range of edges,
+ *   grad w3[i*D + o, k] = sum_e dZ[e, i, o] h[e, k],  grad b3[i*D + o] = sum_e dZ[e, i, o],
+ *   dZ = [Z > 0] x[sender[e], i] g[e, o];
+ * the caller sums the rows (eelg_sum_rows).  Partial-sum rule: the edges are cut into tiles of 32;
+ * a part covers max(32, ceil(tiles / MAXPARTS)) tiles, MAXPARTS = 256 (D = 32) or 64 (D = 64).  So
+ * every part but the last stands for at least 1024 edges (from a few thousand edges on the
+ * partials are about (D+1)/1024 of the [E, D*D] tensor they replace, or less) and they never
+ * exceed 33 MiB (D = 32) / 65 MiB (D = 64) in total (the [E, D*D] tensor at the benchmark's
+ * 1 M edges: 4 GiB / 16 GiB).  The cap is what fills the device: D*D/32 * MAXPARTS one-wave workgroups. */
+#define EELG_NNC_MAXPARTS_32 256
+#define EELG_NNC_MAXPARTS_64 64
+int eelg_nnconv_bwd_w_parts(int n_edges, int D);
+int eelg_nnconv_bwd_w(const float* x, const float* h, const float* w3, const float* b3,
+                      const int* sender, const int* receiver, int n_edges, int D,
+                      const float* grad_agg, float* part, void* stream);
+
 /* Sparse (CSR) x dense with strided operands:
  * out[r*ldo_r + c*ldo_c] = sum_{j in row r} val[j] * B[col[j]*ldb_r + c*ldb_c].
  * Builds the symmetric-contraction coefficients coef = U_sym . W and their weight

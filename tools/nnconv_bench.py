@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Training step of the NNConv benchmark model: fused HIP kernels against the materialised form.
+
+One model (``NNConvNet``, hidden 32, 3 message passes, 'square') at 256 graphs x 1024 nodes /
+4096 edges (``--graphs`` adjustable).  One step = forward + relative-MSE loss + backward +
+grad-norm clip 10 + AdamW(amsgrad), as ``bench.py`` times it on one device.  The fused path and
+``EELG_NNCONV_FUSED=0`` (the same layer as torch on the device, the [E, D*D] per-edge matrices
+formed as PyG does) alternate step by step in one process after a shared warm-up, each step
+timed with device events; per path the median of ``--reps`` steps, graphs/s and the peak of
+``torch.cuda.max_memory_allocated`` over its own steps are reported, plus each kernel's
+median time and its fraction of the fp32-MFMA rate (one layer's kernels at the same edge count,
+timed alone; ``--no-kernels`` skips them), as one JSON line.
+
+usage: python tools/nnconv_bench.py [--reps 10] [--warmup 3] [--graphs 256] [--no-materialised]
+       [--no-kernels]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "energy-equiv-lattice-gnn_amd"))
+
+import torch  # noqa: E402
+
+from argparse import Namespace  # noqa: E402
+
+from gnn import _lib, nnconv  # noqa: E402
+from gnn.data import collate  # noqa: E402
+from gnn.model import EnergyEquivGNN  # noqa: E402
+from gnn.synthetic import SyntheticLattices  # noqa: E402
+from gnn.train import stiffness_loss  # noqa: E402
+
+MFMA_F32_TFLOPS = 155.0   # v_mfma_f32_32x32x2_f32 peak of the device
+
+
+def _timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def kernel_times(d, csr, reps, warmup):
+    """the three kernels alone at the batch's edge count; FLOPs: 2 E D^3 per D x D x D product
+    (forward 1, bwd_edge 2, bwd_w 2)"""
+    lib = _lib.load()
+    e, n = csr.num_edges, csr.num_nodes
+    dev = csr.sender.device
+    x, h = torch.randn(n, d, device=dev), torch.randn(e, d, device=dev).relu()
+    w3, b3 = torch.randn(d * d, d, device=dev) / d ** 0.5, torch.randn(d * d, device=dev)
+    g = torch.randn(n, d, device=dev)
+    msg, gxe, gh = (torch.empty(e, d, device=dev) for _ in range(3))
+    part = torch.empty(int(lib.eelg_nnconv_bwd_w_parts(e, d)), d * d * (d + 1), device=dev)
+    P, s = _lib.ptr, _lib.stream(x)
+    calls = {
+        "nnconv_fwd": (1, lambda: lib.eelg_nnconv_fwd(P(x), P(h), P(w3), P(b3), P(csr.sender), e, d, P(msg), s)),
+        "nnconv_bwd_edge": (2, lambda: lib.eelg_nnconv_bwd_edge(
+            P(x), P(h), P(w3), P(b3), P(csr.sender), P(csr.receiver), e, d, P(g), P(gxe), P(gh), s)),
+        "nnconv_bwd_w": (2, lambda: lib.eelg_nnconv_bwd_w(
+            P(x), P(h), P(w3), P(b3), P(csr.sender), P(csr.receiver), e, d, P(g), P(part), s)),
+    }
+    out = {}
+    for name, (nprod, fn) in calls.items():
+        ms = _timed(fn, reps, warmup)
+        tf = nprod * 2.0 * e * d ** 3 / (ms * 1e-3) / 1e12
+        out[name] = {"ms": round(ms, 4), "tflops": round(tf, 2),
+                     "fraction_of_f32_mfma_peak": round(tf / MFMA_F32_TFLOPS, 4)}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--graphs", type=int, default=256)
+    ap.add_argument("--nodes", type=int, default=1024)
+    ap.add_argument("--edges", type=int, default=4096)
+    ap.add_argument("--hidden", type=int, default=32)
+    ap.add_argument("--layers", type=int, default=3)
+    ap.add_argument("--no-materialised", action="store_true",
+                    help="time the fused path only (the materialised form needs ~3 x E*D*D*4 bytes per layer)")
+    ap.add_argument("--no-kernels", action="store_true", help="skip the per-kernel timings")
+    args = ap.parse_args()
+    dev = "cuda"
+    ds = SyntheticLattices(args.graphs, args.nodes, args.edges, 1234)
+    batch = collate([ds[g] for g in range(args.graphs)]).to(dev)
+    torch.manual_seed(0)
+    model = nnconv.NNConvNet(Namespace(hidden_irreps=args.hidden, message_passes=args.layers,
+                                       positive="square")).to(dev)
+    plist = list(model.parameters())
+    opt = torch.optim.AdamW(plist, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, amsgrad=True,
+                            weight_decay=1e-8, fused=True)
+    csr = EnergyEquivGNN.edge_graph(batch)
+
+    def step(fused):
+        nnconv.NNCONV_FUSED = fused
+        opt.zero_grad(set_to_none=True)
+        loss = stiffness_loss(model(batch)["stiffness"], batch.stiffness)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(plist, 10.0)
+        opt.step()
+        return loss
+    paths = [("fused", True)] + ([] if args.no_materialised else [("materialised", False)])
+    for _ in range(args.warmup):
+        for _, fused in paths:
+            step(fused)
+    torch.cuda.synchronize()
+    times = {k: [] for k, _ in paths}
+    peak = {k: 0 for k, _ in paths}
+    loss = {}
+    for _ in range(args.reps):
+        for key, fused in paths:
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            loss[key] = step(fused)
+            b.record()
+            torch.cuda.synchronize()
+            times[key].append(a.elapsed_time(b))
+            peak[key] = max(peak[key], torch.cuda.max_memory_allocated())
+    nnconv.NNCONV_FUSED = True
+    out = {"shape": f"{args.graphs} x {args.nodes} nodes / {args.edges} edges, hidden {args.hidden}, "
+                    f"{args.layers} passes, fp32", "edges": csr.num_edges,
+           "parameters": sum(p.numel() for p in plist), "reps": args.reps, "warmup": args.warmup}
+    for key, _ in paths:
+        ms = statistics.median(times[key])
+        out[key] = {"step_ms": round(ms, 3), "min_ms": round(min(times[key]), 3),
+                    "max_ms": round(max(times[key]), 3),
+                    "graphs_per_s": round(args.graphs / ms * 1e3, 1),
+                    "max_memory_allocated_mib": round(peak[key] / 2 ** 20, 1),
+                    "loss": round(float(loss[key].item()), 6)}
+    if len(paths) == 2:
+        out["fused_over_materialised_step"] = round(out["fused"]["step_ms"] / out["materialised"]["step_ms"], 4)
+    if not args.no_kernels:
+        out["kernels"] = kernel_times(args.hidden, csr, args.reps, args.warmup)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
