@@ -7,7 +7,7 @@ themselves needs the un-vendored ``lattices`` package and raises.
 """
 from .model import EnergyEquivGNN, GNN_Head  # noqa: F401
 from .synthetic import SyntheticLattices, make_lattice  # noqa: F401
-from .data import Batch, Data, DataLoader, collate  # noqa: F401
+from .data import Batch, Data, DataLoader, collate, degree_stats  # noqa: F401
 from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
 from .design import stiffness_sensitivity  # noqa: F401

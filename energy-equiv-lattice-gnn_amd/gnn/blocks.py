@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import os
 from argparse import Namespace
+from collections.abc import Mapping
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -38,6 +39,33 @@ EdgeIndex = Union[torch.Tensor, ops.EdgeCSR]
 # the fused kernel (the path scripts/train_main.py:32 uses); 'mean' scales its rows by the
 # clamped in-degree; max / min / mul reduce the per-edge messages (ops.per_edge_csr)
 REDUCTIONS = ("sum", "add", "mean", "max", "min", "mul")
+# every accepted interaction_reduction: the torch_scatter reduces and 'pna' (gnn/blocks.py:561-562,
+# 592-594: PNASimple over the per-edge messages, ops.segment_pna), which takes agg_norm_const as
+# the mapping of degree statistics the reference reads (data.degree_stats)
+INTERACTION_REDUCTIONS = REDUCTIONS + ("pna",)
+
+
+class PNASimple(torch.nn.Module):
+    """The parameters of ``gnn/blocks.py:817-848``: ``post_pn = Linear(12, 1, bias=False)`` over
+    the aggregators (mean, min, max, std; outer) times the scalers (identity, amplification,
+    attenuation; inner), and ``avg_deg['log']``.  The aggregation itself is ``ops.segment_pna``
+    on the interaction block's per-edge messages.  The per-component min / max / std are not
+    rotation-equivariant for l > 0: the reference's behaviour, reproduced as it is."""
+
+    def __init__(self, avg_deg):
+        super().__init__()
+        self.avg_deg = {k: float(v) for k, v in avg_deg.items()}
+        self.post_pn = torch.nn.Linear(12, 1, bias=False)
+
+    def forward(self, messages: torch.Tensor, csr: ops.EdgeCSR) -> torch.Tensor:
+        """``messages`` [E, D] in ``csr``'s receiver-sorted order -> [N, D]"""
+        avg_log = self.avg_deg["log"]
+        cache = getattr(csr, "_pna_scalers", None)
+        if cache is None or cache[0] != avg_log:
+            cache = (avg_log, ops.pna_scalers(csr.rowptr, avg_log))
+            csr._pna_scalers = cache
+        return ops.segment_pna(messages, csr.rowptr, csr.num_nodes, self.post_pn.weight, avg_log,
+                               scalers=cache[1])
 
 
 def as_csr(edge_index: EdgeIndex, num_nodes: int, *edge_tensors):
@@ -221,12 +249,25 @@ class TensorProductInteractionBlock(torch.nn.Module):
         self.edge_attrs_irreps = Irreps(edge_attrs_irreps)
         self.edge_feats_irreps = Irreps(edge_feats_irreps)
         self._irreps_out = Irreps(irreps_out)
-        self.agg_norm_const = float(agg_norm_const)
         self.reduce = reduce.lower()
-        if self.reduce not in REDUCTIONS:
+        if self.reduce not in INTERACTION_REDUCTIONS:
             raise NotImplementedError(
                 f"interaction_reduction {reduce!r}: the torch_scatter reduces {sorted(REDUCTIONS)} "
-                "are built ('pna' is out of scope, SURVEY.md section 2)")
+                "and 'pna' are built")
+        if self.reduce == "pna":
+            # the reference reads avg_deg['log'] of this argument (gnn/blocks.py:561-562, gnn/pna.py)
+            if not isinstance(agg_norm_const, Mapping):
+                raise NotImplementedError(
+                    "interaction_reduction 'pna' takes agg_norm_const as the mapping of degree "
+                    "statistics {'log': mean log(in-degree + 1), ...} (gnn.degree_stats), not "
+                    f"{agg_norm_const!r}")
+            if "log" not in agg_norm_const:
+                raise ValueError("interaction_reduction 'pna': agg_norm_const lacks the key 'log' "
+                                 f"(got {sorted(agg_norm_const)}; see gnn.degree_stats)")
+            self.agg_norm_const = dict(agg_norm_const)
+            self.pna = PNASimple(agg_norm_const)
+        else:
+            self.agg_norm_const = float(agg_norm_const)
         # fail at construction, with the supported list, for structures without generated kernels
         kernel_sets.check_tp(self._node_feats_irreps, self.edge_attrs_irreps, self._irreps_out)
         if storage_dtype != torch.float32 and kernel_sets.mul_of(self._node_feats_irreps) != kernel_sets.MUL:
@@ -300,6 +341,10 @@ class TensorProductInteractionBlock(torch.nn.Module):
         x = self.linear_up(node_feats, grad_mailbox=grad_mailbox)
         if w is None:
             w = self.radial_weights(edge_feats)
+        if self.reduce == "pna":
+            # the unscaled per-edge messages, aggregated by PNASimple; no / agg_norm_const here
+            m = ops.tp_interaction(x, edge_attrs, w, ops.per_edge_csr(csr), idx, info, 1.0)
+            return self.linear(self.pna(m, csr)), None
         inv = 1.0 / self.agg_norm_const
         # geometry gradients: the fused / chunked backwards return no SH gradient
         # (bf16 storage: the model refuses at its first forward, ops._tp_bwd_sh at the kernel)

@@ -155,6 +155,17 @@ def build_edge_csr(edge_index: torch.Tensor, num_nodes: int) -> Dict[str, torch.
     }
 
 
+def degree_stats(edge_index: torch.Tensor, num_nodes: int) -> Dict[str, float]:
+    """PNA's dataset statistic over the in-degrees (receivers, ``edge_index[1]``) of a graph or
+    a collated batch: ``{'lin': mean in-degree, 'log': mean log(in-degree + 1)}``, the mapping
+    ``params.agg_norm_const`` holds for ``interaction_reduction='pna'`` (``gnn/pna.py:24-31``
+    reads ``'log'``)."""
+    if num_nodes < 1:
+        raise ValueError(f"degree_stats: num_nodes {num_nodes}")
+    deg = torch.bincount(edge_index[1].reshape(-1).long().cpu(), minlength=num_nodes).double()
+    return {"lin": float(deg.mean()), "log": float(torch.log(deg + 1.0).mean())}
+
+
 def csr_to(csr: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v)
             for k, v in csr.items()}

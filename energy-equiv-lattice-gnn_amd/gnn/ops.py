@@ -418,6 +418,164 @@ def segment_pool_order(src, ptr32, num_graphs: int, reduce: str):
 
 
 # ---------------------------------------------------------------------------
+# principal-neighbourhood aggregation (interaction_reduction = 'pna')
+# ---------------------------------------------------------------------------
+# the fused segment kernels (1), or the composition of the segment sums, the order reductions
+# and torch elementwise ops with the reference's [N, D, 12] stack (0): the memory / time
+# baseline and a second implementation (tools/pna_bench.py, tests/test_gpu_pna.py)
+PNA_FUSED = os.environ.get("EELG_PNA_FUSED", "1") != "0"
+PNA_EPS = 1e-5
+
+
+def pna_scalers(rowptr32: torch.Tensor, avg_log: float) -> torch.Tensor:
+    """[N, 3] fp32 degree scalers of ``PNASimple`` (``gnn/pna.py:20-31``) from the in-degree of
+    the CSR: identity 1, amplification ``log(deg + 1) / avg_log``, attenuation
+    ``avg_log / log(deg + 1)`` (1 where ``deg == 0``)."""
+    deg = (rowptr32[1:] - rowptr32[:-1]).to(torch.float32)
+    lg = torch.log(deg + 1.0)
+    amp = lg / float(avg_log)
+    att = torch.where(deg == 0, torch.ones_like(lg), float(avg_log) / lg.clamp_min(1e-30))
+    return torch.stack([torch.ones_like(lg), amp, att], 1).contiguous()
+
+
+class PNAArgs:
+    """The rows ``segment_pna`` kept as minimum / maximum: ``argmin`` / ``argmax`` [n_rows, width]
+    int32 positions in ``src`` (-1 for an empty segment), filled by the call they were passed to."""
+    argmin: Optional[torch.Tensor] = None
+    argmax: Optional[torch.Tensor] = None
+
+
+class _SegmentPNA(torch.autograd.Function):
+    """``PNASimple.forward`` (``gnn/blocks.py:817-848``) over CSR segments of ``src`` rows on
+    ``eelg_segment_pna_fwd`` / ``_bwd``.  The 12 weights enter through the per-receiver
+    coefficients ``coef[n, k] = sum_s W[3k + s] scalers[n, s]``; their gradient is the fixed-order
+    column sum of ``grad_coef[n, k] scalers[n, s]`` (``sum_rows``).  Saved: ``src`` and four
+    [n_rows, width] buffers; nothing 12-fold is formed."""
+
+    @staticmethod
+    def forward(ctx, src, weight, rowptr, scalers, n_rows: int, args):
+        src = _a16(src)
+        width = src.shape[1]
+        dev = src.device
+        w43 = weight.detach().to(torch.float32).reshape(4, 3)
+        coef = (scalers[:, None, :] * w43[None]).sum(-1).contiguous()       # [N, 4]
+        out = torch.empty(n_rows, width, device=dev, dtype=torch.float32)
+        mean, std = torch.empty_like(out), torch.empty_like(out)
+        amin = torch.empty(n_rows, width, device=dev, dtype=torch.int32)
+        amax = torch.empty_like(amin)
+        # no edges: the kernel reads no row of src, but takes no null pointer
+        s = src if src.numel() else torch.zeros(4, device=dev, dtype=torch.float32)
+        tok = TIMER.start("segment_pna_fwd")
+        _lib.check(_lib.load().eelg_segment_pna_fwd(
+            _lib.ptr(s), _lib.ptr(rowptr), _lib.ptr(coef), n_rows, width, _lib.ptr(out), _lib.ptr(mean),
+            _lib.ptr(std), _lib.ptr(amin), _lib.ptr(amax), _lib.stream(out)), "segment_pna_fwd")
+        TIMER.stop(tok)
+        if args is not None:
+            args.argmin, args.argmax = amin, amax
+        ctx.save_for_backward(src, rowptr, scalers, coef, mean, std, amin, amax)
+        ctx.n_rows, ctx.wshape = n_rows, weight.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        src, rowptr, scalers, coef, mean, std, amin, amax = ctx.saved_tensors
+        g = _a16(g)
+        n_rows, width = ctx.n_rows, src.shape[1]
+        lib = _lib.load()
+        parts = lib.eelg_segment_pna_parts(width)
+        gs = torch.empty_like(src)      # every row is in one segment: written once, no zero fill
+        part = torch.empty(parts, n_rows * 4, device=src.device, dtype=torch.float32)
+        s = src if src.numel() else torch.zeros(4, device=src.device, dtype=torch.float32)
+        o = gs if gs.numel() else torch.empty(4, device=src.device, dtype=torch.float32)
+        tok = TIMER.start("segment_pna_bwd")
+        _lib.check(lib.eelg_segment_pna_bwd(
+            _lib.ptr(s), _lib.ptr(rowptr), _lib.ptr(coef), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(amin),
+            _lib.ptr(amax), _lib.ptr(g), n_rows, width, _lib.ptr(o), _lib.ptr(part), _lib.stream(part)),
+            "segment_pna_bwd")
+        TIMER.stop(tok)
+        gw = None
+        if ctx.needs_input_grad[1]:
+            gcoef = (part[0] if parts == 1 else sum_rows(part)).view(n_rows, 4)
+            # grad W[3k + s] = sum_n grad_coef[n, k] scalers[n, s], rows summed in a fixed order
+            gw = sum_rows((gcoef[:, :, None] * scalers[:, None, :]).reshape(n_rows, 12)).view(ctx.wshape)
+        return (gs if ctx.needs_input_grad[0] else None), gw, None, None, None, None
+
+
+class _SegmentSum(torch.autograd.Function):
+    """``segment_sum_csr`` over segments that cover the rows of ``src``, differentiable in
+    ``src`` (the backward repeats each segment's gradient row over its rows)."""
+
+    @staticmethod
+    def forward(ctx, src, rowptr, n_rows: int):
+        ctx.save_for_backward(rowptr)
+        ctx.n_src = src.shape[0]
+        return segment_sum_csr(src, rowptr, n_rows)
+
+    @staticmethod
+    def backward(ctx, g):
+        (rowptr,) = ctx.saved_tensors
+        return g[_segment_index(rowptr, ctx.n_src)], None, None
+
+
+def _segment_index(rowptr: torch.Tensor, n_src: int) -> torch.Tensor:
+    """[n_src] int64 segment of every row (the segments cover the rows)"""
+    deg = (rowptr[1:] - rowptr[:-1]).long()
+    return torch.repeat_interleave(torch.arange(deg.shape[0], device=rowptr.device), deg,
+                                   output_size=n_src)
+
+
+def _segment_pna_composed(src, rowptr32, n_rows: int, weight, scalers, args):
+    """``segment_pna`` from the ops that predate the fused kernels, autograd through all of it:
+    four [N, D] aggregates, the [N, D, 12] stack of their scaled copies as the reference forms it
+    (``gnn/blocks.py:835-847``), then the 12 weights.  The variance is centred like the kernel's."""
+    src = _f32(src)
+    idx = _segment_index(rowptr32, src.shape[0])
+    deg = (rowptr32[1:] - rowptr32[:-1]).to(torch.float32)
+    inv = (1.0 / deg.clamp_min(1.0))[:, None]
+    mean = _SegmentSum.apply(src, rowptr32, n_rows) * inv
+    d = src - mean[idx]
+    std = torch.sqrt(_SegmentSum.apply(d * d, rowptr32, n_rows) * inv + PNA_EPS)
+    mn = _SegmentOrder.apply(src, rowptr32, n_rows, _ORDER_OPS["min"], True)
+    mx = _SegmentOrder.apply(src, rowptr32, n_rows, _ORDER_OPS["max"], True)
+    if args is not None:            # the kept positions, from the same kernel on the same rows
+        kept = {}
+        for op in ("min", "max"):
+            kept[op] = torch.empty(n_rows, src.shape[1], device=src.device, dtype=torch.int32)
+            val = torch.empty(n_rows, src.shape[1], device=src.device, dtype=torch.float32)
+            _lib.check(_lib.load().eelg_segment_order(
+                _lib.ptr(src.detach()), _lib.ptr(rowptr32), n_rows, src.shape[1], _ORDER_OPS[op],
+                _lib.ptr(val), _lib.ptr(kept[op]), _lib.stream(val)), "segment_order")
+        args.argmin, args.argmax = kept["min"], kept["max"]
+    stack = torch.stack([a * scalers[:, None, s] for a in (mean, mn, mx, std) for s in range(3)], 2)
+    return (stack * weight.reshape(12)).sum(-1)
+
+
+def segment_pna(src, rowptr32, n_rows: int, weight, avg_log: float, scalers=None,
+                args: Optional[PNAArgs] = None):
+    """``PNASimple(avg_deg={'log': avg_log}).forward`` (``gnn/blocks.py:817-848``) of the rows
+    ``src`` [E, width] over the CSR segments ``rowptr32`` (int32, [n_rows + 1], covering every row):
+    ``out[n, c] = sum_k sum_s W[0, 3k + s] scale_s(deg_n) agg_k[n, c]`` with ``agg`` = (mean, min,
+    max, std) and ``scale`` = (identity, amplification, attenuation); ``weight`` is the [1, 12]
+    weight of ``post_pn``.  min / max keep the first extreme of a segment and route their whole
+    gradient there; an empty segment gives ``coef_std * sqrt(1e-5)``.  ``scalers``:
+    ``pna_scalers(rowptr32, avg_log)`` computed ahead (cached per graph by the block).  ``args``:
+    a ``PNAArgs`` that receives the kept positions.  Differentiable in ``src`` and ``weight``;
+    the backward is bitwise repeatable."""
+    _require_device(src, weight)
+    if src.dim() != 2 or src.shape[1] < 1:
+        raise ValueError(f"segment_pna: src [E, width >= 1] expected, got {tuple(src.shape)}")
+    if weight.numel() != 12:
+        raise ValueError(f"segment_pna: the weight of Linear(12, 1), got {tuple(weight.shape)}")
+    if rowptr32.dtype != torch.int32 or rowptr32.shape[0] != n_rows + 1:
+        raise ValueError("segment_pna: rowptr32 is the int32 CSR [n_rows + 1]")
+    if scalers is None:
+        scalers = pna_scalers(rowptr32, avg_log)
+    if not PNA_FUSED:
+        return _segment_pna_composed(src, rowptr32, n_rows, weight, scalers, args)
+    return _SegmentPNA.apply(src, weight, rowptr32.contiguous(), scalers, n_rows, args)
+
+
+# ---------------------------------------------------------------------------
 # fused interaction: gather -> uvu tensor product -> segmented sum / norm
 # ---------------------------------------------------------------------------
 class _TPInteraction(torch.autograd.Function):

@@ -203,6 +203,33 @@ int eelg_segment_order(const float* src, const int* rowptr, int n_rows, int widt
 int eelg_segment_order_bwd(const float* src, const int* rowptr, const int* arg, const float* grad_out,
                            int n_rows, int width, int op, float* grad_src, void* stream);
 
+/* Principal-neighbourhood aggregation over CSR segments of src rows (interaction_reduction =
+ * 'pna'): replaces PNASimple.forward (gnn/blocks.py:817-848; aggregators and scalers of
+ * gnn/pna.py:20-31, 59-78), i.e. six torch_scatter passes, the [N, D, 12] stack of scaled
+ * aggregates and Linear(12, 1), by one pass:
+ *   out[r, c] = coef[r, 0] mean + coef[r, 1] min + coef[r, 2] max + coef[r, 3] std
+ * over the rows rowptr[r]..rowptr[r+1] of src [E, width], with
+ *   mean = sum / max(deg, 1), min / max = the first extreme in row order (as eelg_segment_order),
+ *   std = sqrt(sum (m - mean)^2 / deg + 1e-5)   (centred: >= 0, the reference's relu is a no-op).
+ * coef [n_rows, 4] = sum_s W[3k + s] scale_s(deg) is the caller's (the scalers identity,
+ * log(deg + 1) / avg_log and its inverse, 1 at deg 0).  Saved for the backward: mean, std
+ * [n_rows, width] and argmin, argmax [n_rows, width] (rows of src, -1 for an empty segment, which
+ * gives mean = min = max = 0 and std = sqrt(1e-5)).  Any width >= 1: float4 columns when
+ * width % 4 == 0 (all [., width] buffers 16-byte aligned, -2 otherwise), scalar columns else. */
+int eelg_segment_pna_fwd(const float* src, const int* rowptr, const float* coef, int n_rows, int width,
+                         float* out, float* mean, float* std, int* argmin, int* argmax, void* stream);
+/* Backward: grad_src [E, width], every row of every segment written once (no zero fill when the
+ * segments cover the rows):
+ *   grad_src[e, c] = g (coef_mean / deg + coef_std (m_e - mean) / (deg std)
+ *                       + coef_min [e == argmin] + coef_max [e == argmax]),  g = grad_out[r, c];
+ * and grad_coef_part [eelg_segment_pna_parts(width), n_rows, 4]: the sums of g * (mean, min, max,
+ * std) over each span of columns, in a fixed order (no atomics); grad_coef is their sum over the
+ * leading dimension (eelg_sum_rows). */
+int eelg_segment_pna_parts(int width);
+int eelg_segment_pna_bwd(const float* src, const int* rowptr, const float* coef, const float* mean,
+                         const float* std, const int* argmin, const int* argmax, const float* grad_out,
+                         int n_rows, int width, float* grad_src, float* grad_coef_part, void* stream);
+
 /* Crystal-graph edge convolution (CGC/mCGC benchmark models): replaces
  *   c = cat([x[sender], x[receiver], edge_ft]); msg = softplus(fc_values(c)) * sigmoid(fc_multip(c));
  *   scatter(msg, receiver, reduce)          (scripts/benchmark_models/cgc_modified.py:20-25,
