@@ -11,6 +11,7 @@ from .data import Batch, Data, DataLoader, collate, degree_stats  # noqa: F401
 from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
 from .design import stiffness_sensitivity  # noqa: F401
+from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
 
 __all__ = ["GLAMM_Dataset", "EnergyEquivGNN"]
 classes = __all__

@@ -93,6 +93,9 @@ _SIGS = {
     "eelg_radial_bwd_x": ([_P, _I, _P, _P, _P, _P], _I),
     "eelg_radial_bwd_gh": ([_P, _I, _I, _P, _P, _P, _P], _I),
     "eelg_edge_embed_bwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P], _I),
+    # batch assembly from the device-resident packed dataset
+    "eelg_batch_assemble": ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
+    "eelg_mandel_rotate": ([_P, _I, _P, _P, _I, _P, _P], _I),
 }
 
 LIN_MAXSRC, LIN_MAXSLOT, LINW_MAXINS = 4, 8, 8
@@ -120,6 +123,21 @@ class LinWIns(ctypes.Structure):
 class LinWDesc(ctypes.Structure):
     _fields_ = [("n_ins", _I), ("max_jt", _I), ("max_ut", _I), ("max_rows", _I),
                 ("ins", LinWIns * LINW_MAXINS)]
+
+BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
+
+
+class BatchSrc(ctypes.Structure):
+    _fields_ = [(k, _P) for k in ("positions", "node_attrs", "rowend", "srowend", "sender", "receiver",
+                                  "shifts", "edge_attr", "perm", "sperm")] + \
+               [(k, _I) for k in ("node_w", "edge_w", "total_nodes", "total_edges")]
+
+
+class BatchOut(ctypes.Structure):
+    _fields_ = [(k, _P) for k in ("positions", "node_attrs", "batch", "ptr", "rowptr", "srowptr",
+                                  "edge_index", "shifts", "edge_attr", "perm", "sperm", "sender",
+                                  "receiver")]
+
 
 RADIAL_MAXH = 3
 GATE_MAXBLK = 8

@@ -228,6 +228,40 @@ def rand_rotation(generator: Optional[torch.Generator] = None, dtype=torch.float
     return q.to(dtype)
 
 
+def rand_rotations(n: int, generator: Optional[torch.Generator] = None,
+                   dtype=torch.float64) -> torch.Tensor:
+    """``n`` uniform random proper rotations [n, 3, 3], the batched form of ``rand_rotation``
+    (one fp64 Gaussian draw, one batched QR, sign fix, first column flipped where det < 0).
+    The random stream is its own: not that of ``n`` calls of ``rand_rotation``."""
+    a = torch.randn(n, 3, 3, generator=generator, dtype=torch.float64)
+    q, r = torch.linalg.qr(a)
+    q = q * torch.sign(torch.diagonal(r, dim1=-2, dim2=-1)).unsqueeze(-2)
+    flip = torch.where(torch.linalg.det(q) < 0, -1.0, 1.0).to(q.dtype)
+    q[:, :, 0] = q[:, :, 0] * flip[:, None]
+    return q.to(dtype)
+
+
+# index pair (i, j) of every Mandel index
+_MANDEL_IJ = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+
+
+def mandel_rotation(Q):
+    """The 6x6 Mandel rotation M(Q) of a rotation ``Q`` [..., 3, 3] (numpy or torch), in fp64:
+    ``M C M^T == cart4_to_mandel(einsum('ijkl,ai,bj,ck,dl->abcd', mandel_to_cart4(C), Q, Q, Q, Q))``
+    for a Mandel 6x6 ``C``.  With a <-> (i, j) and b <-> (k, l) of the Mandel order and the
+    weights w: ``M_ab = (w_a / w_b) Q_ik Q_jk`` for b <= 3 and
+    ``(w_a / w_b) (Q_ik Q_jl + Q_il Q_jk)`` for b > 3.  M is orthogonal when Q is."""
+    is_t = torch.is_tensor(Q)
+    q = Q.detach().cpu().double().numpy() if is_t else np.asarray(Q, dtype=np.float64)
+    m = np.zeros((*q.shape[:-2], 6, 6), dtype=np.float64)
+    for a, (i, j) in enumerate(_MANDEL_IJ):
+        for b, (k, l) in enumerate(_MANDEL_IJ):
+            v = q[..., i, k] * q[..., j, k] if b < 3 else \
+                q[..., i, k] * q[..., j, l] + q[..., i, l] * q[..., j, k]
+            m[..., a, b] = (_W[a] / _W[b]) * v
+    return torch.from_numpy(m) if is_t else m
+
+
 class RotateLat:
     """``scripts/train_utils.py:114-146``: rotate positions, shifts and the cartesian
     stiffness / compliance by a random rotation (or ``Q``), then return Mandel targets."""

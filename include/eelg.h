@@ -541,6 +541,71 @@ long long eelg_sum_rows_work(int rows, long long cols);
 int eelg_sum_rows(const float* part, long long ld, int rows, long long cols, float scale, float* out,
                   float* work, long long work_len, void* stream);
 
+/* ---- Batch assembly from a device-resident packed dataset ---------------------------------
+ * Replaces, per training batch, PyG's collation of the sampled graphs (concatenated node / edge
+ * tensors, edge_index offset by the running node count, the sorted `batch` vector and `ptr`;
+ * field layout gnn/datasets.py:256-269), the rotation augmentation RotateLat applies to every
+ * sample (scripts/train_utils.py:114-146: positions and shifts times Q^T, the rank-4 targets by
+ * four factors of Q) and the two stable sorts + two searches that rebuild the receiver / sender
+ * CSR of the collated batch.  The packed dataset holds every graph once: node and edge rows in
+ * the graph's own order, LOCAL sender / receiver indices, and the graph's local CSR (perm, sperm
+ * and the row ends rowptr[1:], srowptr[1:]).  A stable sort by receiver (or sender) of a collated
+ * batch never interleaves graphs, so the batch's CSR is the concatenation of the local ones plus
+ * the output offsets: nothing is sorted here.
+ *
+ * table [4, n_graphs + 1] int32, per slot g of the batch (a graph may fill several slots):
+ *   row 0: first output node (row 0 is strictly increasing: every graph has >= 1 node; entry
+ *          n_graphs = n_nodes),  row 1: first output edge (entry n_graphs = n_edges),
+ *   row 2: first node of the slot's graph in the packed tensors,  row 3: its first edge
+ *   (entry n_graphs of rows 2 and 3 is not read).
+ * rot [n_graphs, 3, 3] (may be NULL): positions and shifts of slot g become Q_g v (row form
+ * v Q_g^T, three fmaf in the order k = 0, 1, 2); NULL copies them unmultiplied.
+ * Outputs, per output node i of slot g (source row s): positions, node_attrs, batch[i] = g
+ * (int64), rowptr[i + 1] = rowend[s] + edge offset (likewise srowptr; entry 0 = 0), and
+ * ptr[g + 1] = the slot's node end (int64 [n_graphs + 1]).  Per output edge j of slot g (source
+ * row s): edge_index[0 / 1][j] = local sender / receiver + node offset (int64 [2, n_edges], the
+ * graph's own edge order), shifts, edge_attr, perm[j] = local perm + edge offset (int64),
+ * sperm[j] likewise (int32), sender[j] / receiver[j] = the endpoints of the graph's edge perm[s]
+ * + node offset (int32, receiver-sorted order).
+ * One launch, one thread per output node and per output edge; everything fp32 / integer copies,
+ * no atomics: bitwise repeatable.  Rows are 12 bytes, so there is no float4 path.  A source row
+ * outside [0, total_nodes) / [0, total_edges) (a corrupt table) is skipped, not read.
+ * -2: negative sizes, node_w / edge_w outside 1..EELG_BATCH_MAXW, null pointers.  n_graphs == 0
+ * (or n_nodes == 0): nothing is launched, 0 is returned.  n_edges == 0: the edge outputs may be
+ * NULL. */
+#define EELG_BATCH_MAXW 64
+typedef struct {
+  const float* positions;   /* [total_nodes, 3] */
+  const float* node_attrs;  /* [total_nodes, node_w] */
+  const int* rowend;        /* [total_nodes] local rowptr[1:] of each graph */
+  const int* srowend;       /* [total_nodes] local srowptr[1:] */
+  const int* sender;        /* [total_edges] local, the graph's own edge order */
+  const int* receiver;
+  const float* shifts;      /* [total_edges, 3] */
+  const float* edge_attr;   /* [total_edges, edge_w] */
+  const int* perm;          /* [total_edges] local receiver-sorted order */
+  const int* sperm;         /* [total_edges] local sender order over it */
+  int node_w, edge_w, total_nodes, total_edges;
+} eelg_batch_src;
+typedef struct {
+  float* positions; float* node_attrs; int64_t* batch; int64_t* ptr; int* rowptr; int* srowptr;
+  int64_t* edge_index; float* shifts; float* edge_attr; int64_t* perm; int* sperm; int* sender;
+  int* receiver;
+} eelg_batch_out;
+int eelg_batch_assemble(const eelg_batch_src* src, const int* table, const float* rot, int n_graphs,
+                        int n_nodes, int n_edges, const eelg_batch_out* out, void* stream);
+
+/* Per-graph Mandel 6x6 targets of a batch: out[g] = M(Q_g) src[sel[g]] M(Q_g)^T, the Mandel form
+ * of RotateLat's rank-4 rotation einsum('ijkl,ai,bj,ck,dl->abcd') (scripts/train_utils.py:
+ * 131-136) followed by the cartesian -> Mandel conversion.  Mandel order 11, 22, 33, 23, 13, 12,
+ * weights w = (1, 1, 1, r2, r2, r2), r2 = sqrt(2); for a <-> (i, j), b <-> (k, l):
+ *   M_ab = (w_a / w_b) Q_ik Q_jk (b <= 3),  (w_a / w_b) (Q_ik Q_jl + Q_il Q_jk) (b > 3).
+ * src [n_src, 6, 6], sel [n_graphs] int32 rows of src, rot [n_graphs, 3, 3] or NULL (out[g] =
+ * src[sel[g]], copied), out [n_graphs, 6, 6].  One thread per output entry; fixed order.
+ * A sel entry outside [0, n_src) is skipped.  -2: negative sizes, null pointers. */
+int eelg_mandel_rotate(const float* src, int n_src, const int* sel, const float* rot, int n_graphs,
+                       float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
