@@ -12,6 +12,8 @@ from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
 from .design import stiffness_sensitivity  # noqa: F401
 from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
+from .metrics import (METRIC_COLUMNS, ErrorTable, aggr_errors, evaluate, metric_directions,  # noqa: F401
+                      obtain_errors, stiffness_metrics, validation_metrics)
 
 __all__ = ["GLAMM_Dataset", "EnergyEquivGNN"]
 classes = __all__

@@ -96,6 +96,8 @@ _SIGS = {
     # batch assembly from the device-resident packed dataset
     "eelg_batch_assemble": ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
     "eelg_mandel_rotate": ([_P, _I, _P, _P, _I, _P, _P], _I),
+    # validation / test metrics of predicted stiffness matrices
+    "eelg_stiffness_metrics": ([_P, _P, _P, _I, _I, _F, _P, _P], _I),
 }
 
 LIN_MAXSRC, LIN_MAXSLOT, LINW_MAXINS = 4, 8, 8
@@ -125,6 +127,7 @@ class LinWDesc(ctypes.Structure):
                 ("ins", LinWIns * LINW_MAXINS)]
 
 BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
+METRICS_COLS = 16        # include/eelg.h EELG_METRICS_COLS
 
 
 class BatchSrc(ctypes.Structure):

@@ -3,7 +3,9 @@ without the Lightning runtime (not installed; its control plane is out of scope)
 
 ``training_step`` computes the reference loss
 ``100 * mean_b( mean_ij (C - C^)^2 / mean_ij C^2 )``; ``configure_optimizers``
-builds the same AdamW(amsgrad) (``scripts/train_utils.py:38-43``).
+builds the same AdamW(amsgrad) (``scripts/train_utils.py:38-43``); ``validation_step``
+computes the reference's two validation metrics (``scripts/train_utils.py:66-89``)
+through ``gnn.metrics``.
 """
 from __future__ import annotations
 
@@ -11,6 +13,8 @@ from argparse import Namespace
 from typing import Any
 
 import torch
+
+from .metrics import metric_directions, validation_metrics
 
 
 def stiffness_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -38,6 +42,17 @@ class LightningWrappedModel(torch.nn.Module):
     def training_step(self, batch, batch_idx: int = 0) -> torch.Tensor:
         out = self.model(batch)
         return stiffness_loss(out["stiffness"], batch["stiffness"])
+
+    def validation_step(self, batch, batch_idx: int = 0, directions=None) -> torch.Tensor:
+        """``val_loss`` (MSE over all entries); both metrics (``val_loss``, ``val_stiff_dir_loss``:
+        the L1 of the directional stiffness over ``directions``, 250 fresh random unit vectors by
+        default) are left in ``self.val_metrics`` as 0-dim tensors on the batch's device."""
+        with torch.no_grad():
+            pred = self.model(batch)["stiffness"]
+            if directions is None:
+                directions = metric_directions(250, device=pred.device)
+            self.val_metrics = validation_metrics(pred, batch["stiffness"], directions)
+        return self.val_metrics["val_loss"]
 
     def predict_step(self, batch, batch_idx: int = 0):
         return self.model(batch), batch

@@ -606,6 +606,37 @@ int eelg_batch_assemble(const eelg_batch_src* src, const int* table, const float
 int eelg_mandel_rotate(const float* src, int n_src, const int* sel, const float* rot, int n_graphs,
                        float* out, void* stream);
 
+/* ---- Validation / test metrics of predicted stiffness matrices -----------------------------
+ * One launch for what LightningWrappedModel.validation_step (scripts/train_utils.py:66-89) and
+ * obtain_errors (scripts/train_utils.py:149-171) compute per graph: stiffness_Mandel_to_cart_4,
+ * einsum('...ijkl,pi,pj,pk,pl->...p') of target and prediction over [B, 3, 3, 3, 3], and two
+ * torch.linalg.eigvalsh calls on [B, 6, 6].
+ * pred, target [n_graphs, 6, 6] fp32 Mandel (order 11, 22, 33, 23, 13, 12, as eelg_mandel_rotate),
+ * dirs [n_dirs, 3] unit vectors, out [n_graphs, EELG_METRICS_COLS].  Both matrices are multiplied
+ * by `scale` first (obtain_errors: 10, validation: 1; the products are rounded to fp32 before any
+ * difference is taken).  Row of graph g:
+ *   0 mseloss         mean_ij (C^ - C)^2
+ *   1 loss            mean_ij |C^ - C|
+ *   2 dir_loss        mean_p |c_p - c^_p|,  c_p = v_p^T C v_p,
+ *                     v = (d1^2, d2^2, d3^2, r2 d2 d3, r2 d1 d3, r2 d1 d2), r2 = sqrt(2): the
+ *                     reference's einsum over the cartesian tensor, also for a C that is not
+ *                     exactly symmetric; no rank-4 tensor is formed
+ *   3 mean_stiffness  mean_p c_p of the target
+ *   4..9   target_eig     eigenvalues of the target, ascending
+ *   10..15 predicted_eig  eigenvalues of the prediction, ascending
+ * Eigenvalues: cyclic Jacobi in fp32 (csrc/eelg_jacobi.h) on the symmetric matrix taken from the
+ * LOWER triangle (eigvalsh's UPLO = 'L': the upper triangle is never read), a fixed number of
+ * sweeps (EELG_JACOBI_SWEEPS), so any input terminates; a NaN input gives NaN in the columns that
+ * depend on it and in no other graph's row.
+ * One wavefront per graph, directions strided over the lanes, fixed xor-butterfly sums; no LDS,
+ * scratch or atomics.  A graph's row depends on (its two matrices, dirs, n_dirs, scale) alone:
+ * bitwise equal in any batch, at any position, on every run.
+ * n_graphs == 0: nothing is launched, 0 is returned whatever the pointers.  -2: n_graphs < 0,
+ * n_dirs <= 0, a null pointer. */
+#define EELG_METRICS_COLS 16
+int eelg_stiffness_metrics(const float* pred, const float* target, const float* dirs, int n_graphs,
+                           int n_dirs, float scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
