@@ -583,8 +583,9 @@ static dim3 tp_fwd_grid(const eelg_tp_cfg& c, int n_nodes, bool bf = false) {
   return dim3(((tiles + 7) / 8) * 8 * (bf ? c.ngroups_bf : c.ngroups));
 }
 
-int eelg_tp_fwd(int cfg, const float* x, const float* sh, const float* w, const int* sender,
-                const int* rowptr, int n_nodes, float inv_norm, float* agg, void* stream) {
+int eelg_tp_fwd_rows(int cfg, const float* x, const float* sh, const float* w, const int* wrow,
+                     const int* sender, const int* rowptr, int n_nodes, float inv_norm, float* agg,
+                     void* stream) {
   const eelg_tp_cfg* c = tp_cfg(cfg);
   if (!c) return -1;
   if (n_nodes <= 0) return 0;
@@ -594,12 +595,18 @@ int eelg_tp_fwd(int cfg, const float* x, const float* sh, const float* w, const 
         reinterpret_cast<uintptr_t>(w)) & 15) != 0)
     return fail(-2, "tp_fwd: x, sh and w must be 16-byte aligned");
   hipLaunchKernelGGL(c->fwd, tp_fwd_grid(*c, n_nodes), dim3(64 * c->fwpb), 0, (hipStream_t)stream, x,
-                     sh, w, sender, rowptr, n_nodes, inv_norm, agg);
+                     sh, w, sender, rowptr, n_nodes, inv_norm, agg, wrow ? wrow : sender, wrow ? 1 : 0);
   return check_launch("tp_fwd");
 }
 
-int eelg_tp_fwd_bf16(int cfg, const float* x, const float* sh, const void* w, const int* sender,
-                     const int* rowptr, int n_nodes, float inv_norm, float* agg, void* stream) {
+int eelg_tp_fwd(int cfg, const float* x, const float* sh, const float* w, const int* sender,
+                const int* rowptr, int n_nodes, float inv_norm, float* agg, void* stream) {
+  return eelg_tp_fwd_rows(cfg, x, sh, w, nullptr, sender, rowptr, n_nodes, inv_norm, agg, stream);
+}
+
+int eelg_tp_fwd_rows_bf16(int cfg, const float* x, const float* sh, const void* w, const int* wrow,
+                          const int* sender, const int* rowptr, int n_nodes, float inv_norm,
+                          float* agg, void* stream) {
   const eelg_tp_cfg* c = tp_cfg(cfg);
   if (!c) return -1;
   if (!c->fwd_bf) return fail(-2, "tp_fwd_bf16: bf16 storage is generated for mul 32 only (config %s)", c->name);
@@ -610,8 +617,14 @@ int eelg_tp_fwd_bf16(int cfg, const float* x, const float* sh, const void* w, co
     return fail(-2, "tp_fwd_bf16: x, sh and w must be 16-byte aligned");
   hipLaunchKernelGGL(c->fwd_bf, tp_fwd_grid(*c, n_nodes, true), dim3(64 * c->fwpb), 0, (hipStream_t)stream,
                      x, sh, static_cast<const unsigned short*>(w), sender, rowptr, n_nodes, inv_norm,
-                     agg);
+                     agg, wrow ? wrow : sender, wrow ? 1 : 0);
   return check_launch("tp_fwd_bf16");
+}
+
+int eelg_tp_fwd_bf16(int cfg, const float* x, const float* sh, const void* w, const int* sender,
+                     const int* rowptr, int n_nodes, float inv_norm, float* agg, void* stream) {
+  return eelg_tp_fwd_rows_bf16(cfg, x, sh, w, nullptr, sender, rowptr, n_nodes, inv_norm, agg,
+                               stream);
 }
 
 // tp_bwd: 8 half-waves x beph edges per block; with bxcd the grid is 1-D, the edge blocks rounded
@@ -622,16 +635,23 @@ static dim3 tp_bwd_grid(const eelg_tp_cfg& c, int n_edges) {
   return dim3(((nb + 7) / 8) * 8 * c.nbgroups);
 }
 
-int eelg_tp_bwd_sorted(int cfg, const float* x, const float* sh, const float* w, const int* sender,
-                       const int* receiver, const int* spos, int n_edges, const float* grad_agg,
-                       float inv_norm, float* grad_w, float* gxe, void* stream) {
+int eelg_tp_bwd_rows(int cfg, const float* x, const float* sh, const float* w, const int* wrow,
+                     const int* sender, const int* receiver, const int* spos, int n_edges,
+                     const float* grad_agg, float inv_norm, float* grad_w, float* gxe, void* stream) {
   const eelg_tp_cfg* c = tp_cfg(cfg);
   if (!c) return -1;
   if (n_edges <= 0) return 0;
   hipLaunchKernelGGL(c->bwd, tp_bwd_grid(*c, n_edges), dim3(256), 0,
                      (hipStream_t)stream, x, sh, w, sender, receiver, n_edges, grad_agg, inv_norm,
-                     grad_w, gxe, spos);
+                     grad_w, gxe, spos, wrow);
   return check_launch("tp_bwd");
+}
+
+int eelg_tp_bwd_sorted(int cfg, const float* x, const float* sh, const float* w, const int* sender,
+                       const int* receiver, const int* spos, int n_edges, const float* grad_agg,
+                       float inv_norm, float* grad_w, float* gxe, void* stream) {
+  return eelg_tp_bwd_rows(cfg, x, sh, w, nullptr, sender, receiver, spos, n_edges, grad_agg,
+                          inv_norm, grad_w, gxe, stream);
 }
 
 int eelg_tp_bwd(int cfg, const float* x, const float* sh, const float* w, const int* sender,
@@ -641,10 +661,10 @@ int eelg_tp_bwd(int cfg, const float* x, const float* sh, const float* w, const 
                             grad_w, gxe, stream);
 }
 
-int eelg_tp_bwd_sorted_bf16(int cfg, const float* x, const float* sh, const void* w,
-                            const int* sender, const int* receiver, const int* spos, int n_edges,
-                            const float* grad_agg, float inv_norm, void* grad_w, void* gxe,
-                            void* stream) {
+int eelg_tp_bwd_rows_bf16(int cfg, const float* x, const float* sh, const void* w, const int* wrow,
+                          const int* sender, const int* receiver, const int* spos, int n_edges,
+                          const float* grad_agg, float inv_norm, void* grad_w, void* gxe,
+                          void* stream) {
   const eelg_tp_cfg* c = tp_cfg(cfg);
   if (!c) return -1;
   if (!c->bwd_bf) return fail(-2, "tp_bwd_bf16: bf16 storage is generated for mul 32 only (config %s)", c->name);
@@ -652,8 +672,16 @@ int eelg_tp_bwd_sorted_bf16(int cfg, const float* x, const float* sh, const void
   hipLaunchKernelGGL(c->bwd_bf, tp_bwd_grid(*c, n_edges), dim3(256), 0,
                      (hipStream_t)stream, x, sh, static_cast<const unsigned short*>(w), sender,
                      receiver, n_edges, grad_agg, inv_norm, static_cast<unsigned short*>(grad_w),
-                     static_cast<unsigned short*>(gxe), spos);
+                     static_cast<unsigned short*>(gxe), spos, wrow);
   return check_launch("tp_bwd_bf16");
+}
+
+int eelg_tp_bwd_sorted_bf16(int cfg, const float* x, const float* sh, const void* w,
+                            const int* sender, const int* receiver, const int* spos, int n_edges,
+                            const float* grad_agg, float inv_norm, void* grad_w, void* gxe,
+                            void* stream) {
+  return eelg_tp_bwd_rows_bf16(cfg, x, sh, w, nullptr, sender, receiver, spos, n_edges, grad_agg,
+                               inv_norm, grad_w, gxe, stream);
 }
 
 int eelg_tp_bwd_bf16(int cfg, const float* x, const float* sh, const void* w, const int* sender,

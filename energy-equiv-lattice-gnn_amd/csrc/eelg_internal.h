@@ -3,16 +3,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// the last arguments of the four tp_fwd / tp_bwd forms: the per-edge weight-row index
+// (eelg_tp_fwd_rows / eelg_tp_bwd_rows).  tp_bwd: optional, null = every edge its own row.
+// tp_fwd: (wrow, wst) with wrow never null -- wst = 0 means every edge its own row and wrow any
+// readable [E] int array (gen_kernels._emit_tp_fwd_glds2)
 typedef void (*eelg_tp_fwd_fn)(const float*, const float*, const float*, const int*, const int*, int,
-                               float, float*);
+                               float, float*, const int*, int);
 typedef void (*eelg_tp_bwd_fn)(const float*, const float*, const float*, const int*, const int*, int,
-                               const float*, float, float*, float*, const int*);
+                               const float*, float, float*, float*, const int*, const int*);
 // bf16 storage (bit patterns in unsigned short) of the edge-sized TP tensors
 typedef void (*eelg_tp_fwd_bf_fn)(const float*, const float*, const unsigned short*, const int*,
-                                  const int*, int, float, float*);
+                                  const int*, int, float, float*, const int*, int);
 typedef void (*eelg_tp_bwd_bf_fn)(const float*, const float*, const unsigned short*, const int*,
                                   const int*, int, const float*, float, unsigned short*,
-                                  unsigned short*, const int*);
+                                  unsigned short*, const int*, const int*);
 // sender-order backward: (x, sh, w, sperm, srowptr, receiver, n_nodes, grad_agg, inv_norm,
 // grad_w, grad_x)
 typedef void (*eelg_tp_bws_fn)(const float*, const float*, const float*, const int*, const int*,

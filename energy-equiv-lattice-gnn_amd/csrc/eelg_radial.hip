@@ -73,6 +73,11 @@ __device__ __forceinline__ float rad_ld(const float* __restrict__ p, size_t idx,
   return ok ? v : 0.0f;
 }
 
+// clamped index load + select (masked lanes read element 0 and get 0)
+__device__ __forceinline__ int rad_ldi(const int* __restrict__ p, int i, bool ok) {
+  const int v = p[ok ? i : 0];
+  return ok ? v : 0;
+}
 // fast exp / reciprocal (a few ulp; the parity bound is 1e-5 of max)
 __device__ __forceinline__ float rad_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
 __device__ __forceinline__ float rad_silu(float z) { return z * rad_sigmoid(z); }
@@ -706,10 +711,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(rad_s2_wpe<
 // linear weight-gradient kernel and eelg_sum_rows run (gnn/ops.py): the fused form kept 96
 // accumulator registers per wave across its tiles and ran at one to two waves per SIMD with
 // scratch spills (0.24 ms at the bench shape, 11.5 % MFMA busy, profiles/r04l_pmc.md).
+// zrow (eelg_radial_bwd_chain_rows; null otherwise): the MLP ran on n_zrows shared rows and edge
+// e's pre-activations are row zrow[e] of zsave [NH, n_zrows, H]; everything else is per edge.
+// The last layer's rows are then also written per edge to zlast [E, H], which radial_bwd_wo
+// streams: gathering them there, behind an index load in each of its column blocks, doubled
+// that kernel's time (146 -> 323 us at the bench shape).
 template <int H, int NH>
 __global__ __launch_bounds__(256) void radial_bwd_chain_kernel(
     const float* __restrict__ ghin, int n_edges, eelg_radial_desc d, const float* __restrict__ zsave,
-    float* __restrict__ gz, float* __restrict__ hin) {
+    float* __restrict__ gz, float* __restrict__ hin, const int* __restrict__ zrow, int n_zrows,
+    float* __restrict__ zlast) {
   constexpr int HS = H + 1, NT = H / 32, KH = H / 2, NHM = NH > 1 ? NH - 1 : 1;
   __shared__ float G[4 * 32 * HS];
   __shared__ float WS[NHM * H * H];   // W_1 .. W_{NH-1} (the chain's B operand)
@@ -717,8 +728,10 @@ __global__ __launch_bounds__(256) void radial_bwd_chain_kernel(
   const int ntile = (n_edges + 31) >> 5;
   float* __restrict__ gw_ = G + wave * 32 * HS;
   const uint32_t E32 = (uint32_t)n_edges;
+  const uint32_t Z32 = zrow ? (uint32_t)n_zrows : E32;   // rows of zsave per layer
   const rad_rsrc_t rgh = rad_rsrc(ghin, E32 * H * 4u);
-  const rad_rsrc_t rzs = rad_rsrc(zsave, (uint32_t)NH * E32 * H * 4u);
+  const rad_rsrc_t rzl = rad_rsrc(zlast, zrow ? E32 * H * 4u : 0u);   // no zrow: every store dropped
+  const rad_rsrc_t rzs = rad_rsrc(zsave, (uint32_t)NH * Z32 * H * 4u);
   const rad_rsrc_t rgz = rad_rsrc(gz, (uint32_t)NH * E32 * H * 4u);
   const rad_rsrc_t rhi = rad_rsrc(hin, (uint32_t)NHM * E32 * H * 4u);
 #pragma unroll
@@ -728,14 +741,22 @@ __global__ __launch_bounds__(256) void radial_bwd_chain_kernel(
   for (int t = blockIdx.x * 4 + wave; t < ntile; t += gridDim.x * 4) {
     const int e0 = t * 32;
     rad_f32x16 gh[NT], zc[NT];
+    int zr[16];   // the zsave row of each of this lane's 16 edges
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = e0 + rad_row(r, hf);
+      zr[r] = zrow ? rad_ldi(zrow, row, row < n_edges) : row;
+    }
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = e0 + rad_row(r, hf);
         const uint32_t o = ((uint32_t)row * H + ct * 32 + i) * 4u;
+        const uint32_t oz = ((uint32_t)zr[r] * H + ct * 32 + i) * 4u;
         gh[ct][r] = rad_bld(rgh, rad_off(o, row < n_edges));
-        zc[ct][r] = rad_bld(rzs, rad_off((uint32_t)(NH - 1) * E32 * H * 4u + o, row < n_edges));
+        zc[ct][r] = rad_bld(rzs, rad_off((uint32_t)(NH - 1) * Z32 * H * 4u + oz, row < n_edges));
+        if (zrow) rad_bst(rzl, rad_off(o, row < n_edges), zc[ct][r]);
       }
 #pragma unroll
     for (int n = NH - 1; n >= 0; --n) {
@@ -757,7 +778,8 @@ __global__ __launch_bounds__(256) void radial_bwd_chain_kernel(
           for (int r = 0; r < 16; ++r) {
             const int row = e0 + rad_row(r, hf);
             const uint32_t o = ((uint32_t)row * H + ct * 32 + i) * 4u;
-            zc[ct][r] = rad_bld(rzs, rad_off((uint32_t)(n - 1) * E32 * H * 4u + o, row < n_edges));
+            const uint32_t oz = ((uint32_t)zr[r] * H + ct * 32 + i) * 4u;
+            zc[ct][r] = rad_bld(rzs, rad_off((uint32_t)(n - 1) * Z32 * H * 4u + oz, row < n_edges));
             rad_bst(rhi, rad_off((uint32_t)(n - 1) * E32 * H * 4u + o, row < n_edges), rad_silu(zc[ct][r]));
           }
         // grad_h of the layer below: gh[e][c] = sum_j gz[e][j] W_n[j][c] (the wave's rows on the
@@ -793,10 +815,11 @@ __global__ __launch_bounds__(256) void radial_bwd_chain_kernel(
 // loads its 16 values (coalesced over j), splits them (bf16 storage: one exact part).  B[e][k] =
 // SiLU(z_last[e][k]) is computed, split and stored in LDS in fragment order once per workgroup by
 // all its threads (one fragment per thread at H = 64), double buffered.
+// zlast: the last hidden layer's pre-activations [E, H], one row per edge.
 template <int H, int NH, bool BF>
 __global__ __launch_bounds__(256) void radial_bwd_wo_kernel(const void* __restrict__ gw,
                                                             int n_edges, int W,
-                                                            const float* __restrict__ zsave,
+                                                            const float* __restrict__ zlast,
                                                             int tiles_per_split,
                                                             float* __restrict__ part) {
   constexpr int NT = H / 32, ES = BF ? 2 : 4;
@@ -809,7 +832,7 @@ __global__ __launch_bounds__(256) void radial_bwd_wo_kernel(const void* __restri
   const int t0 = s * tiles_per_split, t1 = min(ntile, t0 + tiles_per_split);
   const uint32_t E = (uint32_t)n_edges;
   const rad_rsrc_t rg = rad_rsrc(gw, E * (uint32_t)W * ES);
-  const rad_rsrc_t rz = rad_rsrc(zsave + (size_t)(NH - 1) * E * H, E * (uint32_t)H * 4u);
+  const rad_rsrc_t rz = rad_rsrc(zlast, E * (uint32_t)H * 4u);
   // the B fragment this thread builds: (ct, kb, hf, k) = decomposition of threadIdx.x
   const bool bmine = threadIdx.x < NFR;
   const int bk = threadIdx.x & 31, bh = (threadIdx.x >> 5) & 1, bkb = (threadIdx.x >> 6) & 1,
@@ -1101,14 +1124,46 @@ int eelg_radial_bwd_chain(const void* grad_w, int grad_bf16, int n_edges, const 
   const int ntile = (n_edges + 31) / 32;
   const dim3 g2((unsigned)((ntile + 3) / 4 < 2048 ? (ntile + 3) / 4 : 2048));
   if (d->n_hidden == 1)
-    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 1>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin);
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 1>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, (const int*)nullptr, 0, (float*)nullptr);
   else if (d->n_hidden == 2)
-    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 2>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin);
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 2>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, (const int*)nullptr, 0, (float*)nullptr);
   else
-    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 3>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin);
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 3>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, (const int*)nullptr, 0, (float*)nullptr);
   if (int rc = eelg_check_launch("radial_bwd_chain")) return rc;
   const dim3 g3((W + 127) / 128, ns);
-  RAD_LAUNCH3(radial_bwd_wo_kernel, g3, grad_w, n_edges, W, zsave, tps, part_wo);
+  RAD_LAUNCH3(radial_bwd_wo_kernel, g3, grad_w, n_edges, W, zsave + (size_t)(d->n_hidden - 1) * n_edges * d->hidden, tps, part_wo);
+  return eelg_check_launch("radial_bwd_wo");
+}
+
+int eelg_radial_bwd_chain_rows(const void* grad_w, int grad_bf16, int n_edges, const int* zrow,
+                               int n_rows, const eelg_radial_desc* d, const void* wot_parts,
+                               const float* zsave, float* grad_h, float* gz, float* hin,
+                               float* zlast, float* part_wo, void* stream) {
+  if (int rc = radial_check(d, n_edges, grad_bf16 ? 2 : 4)) return rc;
+  if (!rad_a16(wot_parts) || !rad_a16(grad_w))
+    return eelg_fail(-2, "radial_bwd_chain_rows: grad_w and wot_parts must be 16-byte aligned");
+  if (d->hidden != 64) return eelg_fail(-2, "radial_bwd_chain_rows: hidden %d not built (64)", d->hidden);
+  if (n_edges == 0) return 0;
+  if (!zrow || !zlast || n_rows < 1 || n_rows > n_edges)
+    return eelg_fail(-2, "radial_bwd_chain_rows: %d shared rows for %d edges", n_rows, n_edges);
+  const unsigned short* wotp = static_cast<const unsigned short*>(wot_parts);
+  hipStream_t st = (hipStream_t)stream;
+  const bool bf = grad_bf16 != 0;
+  int nw, ns, tps;
+  radial_plan(n_edges, d->n_out, &nw, &ns, &tps);
+  const int W = d->n_out;
+  if (int rc = rad_launch_gh(grad_w, bf, n_edges, d, wotp, grad_h, st)) return rc;
+  const int ntile = (n_edges + 31) / 32;
+  const dim3 g2((unsigned)((ntile + 3) / 4 < 2048 ? (ntile + 3) / 4 : 2048));
+  if (d->n_hidden == 1)
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 1>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, zrow, n_rows, zlast);
+  else if (d->n_hidden == 2)
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 2>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, zrow, n_rows, zlast);
+  else
+    hipLaunchKernelGGL((radial_bwd_chain_kernel<64, 3>), g2, dim3(256), 0, st, grad_h, n_edges, *d, zsave, gz, hin, zrow, n_rows, zlast);
+  if (int rc = eelg_check_launch("radial_bwd_chain")) return rc;
+  const dim3 g3((W + 127) / 128, ns);
+  RAD_LAUNCH3(radial_bwd_wo_kernel, g3, grad_w, n_edges, W, zlast, tps, part_wo);
   return eelg_check_launch("radial_bwd_wo");
 }
 
@@ -1165,7 +1220,7 @@ int eelg_radial_bwd(const void* grad_w, int grad_bf16, int n_edges, const eelg_r
 #undef RAD_SMALL2
   if (int rc = eelg_check_launch("radial_bwd_small")) return rc;
   const dim3 g3((W + 127) / 128, ns);
-  RAD_LAUNCH3(radial_bwd_wo_kernel, g3, grad_w, n_edges, W, zsave, tps, part_wo);
+  RAD_LAUNCH3(radial_bwd_wo_kernel, g3, grad_w, n_edges, W, zsave + (size_t)(d->n_hidden - 1) * n_edges * d->hidden, tps, part_wo);
   return eelg_check_launch("radial_bwd_wo");
 }
 

@@ -537,7 +537,13 @@ def _emit_tp_fwd_glds2(name, groups, din, nshp, dmid, wn, node_off, bf: bool = F
     L.append(f"__global__ __launch_bounds__({64 * WPB}){wpe} void tp_fwd_{name}{'_bw' if bf else ''}(")
     L.append(f"    const float* __restrict__ x, const float* __restrict__ sh, const {WT}* __restrict__ w,")
     L.append("    const int* __restrict__ sender, const int* __restrict__ rowptr, int n_nodes,")
-    L.append("    float inv_norm, float* __restrict__ agg) {")
+    # wst = 1: edge e reads weight row wrow[e] (rows shared by the two directions of a strut,
+    # gnn/ops.py StrutMap); wst = 0: row e, and wrow is any readable [E] int array (the host
+    # passes sender).  Never null: the index load must mirror the sender load exactly, one
+    # unconditional scalar load -- with a null test on the pointer (in the loop or hoisted) hipcc
+    # made it a vector load, whose vmcnt(0) wait retired the LDS-DMA rows in flight
+    # (tp_fwd_tpB_l4 405 -> 449 us, tp_fwd_tpA_l4 47 -> 71 us per launch)
+    L.append("    float inv_norm, float* __restrict__ agg, const int* __restrict__ wrow, int wst) {")
     L.append(f"  __shared__ float4 img_[{WPB}][{NBUF}][2][{NI}];   // [wave][buffer][half][chunk]")
     L.append("  const int lane = threadIdx.x & 63, hf = lane >> 5;")
     L.append("  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);")
@@ -574,7 +580,9 @@ def _emit_tp_fwd_glds2(name, groups, din, nshp, dmid, wn, node_off, bf: bool = F
                 out.append(f"        const int ss_ = *(ok_ ? sender + ee_ : reinterpret_cast<const int*>(pad_));   // never a load through a null sender (E = 0)")
                 out.append(f"        const char* xb = ok_ ? reinterpret_cast<const char*>(x + (size_t)ss_ * {din}) : pad_;")
                 out.append(f"        const char* shb = ok_ ? reinterpret_cast<const char*>(sh + (size_t)ee_ * {nshp}) : pad_;")
-                out.append(f"        const char* wb = ok_ ? reinterpret_cast<const char*>(w + (size_t)ee_ * {wn}) : pad_;")
+                out.append(f"        const int wq_ = *(ok_ ? wrow + ee_ : reinterpret_cast<const int*>(pad_));   // as ss_: a scalar load")
+                out.append(f"        const int wr_ = wst ? wq_ : ee_;")
+                out.append(f"        const char* wb = ok_ ? reinterpret_cast<const char*>(w + (size_t)wr_ * {wn}) : pad_;")
                 out.append(f"        float4* dst = ib + ({buf}) * {2 * NI} + {h * NI};")
                 for j in range(nj):
                     # cache policy 2 = nt on gfx950: an instruction that moves only weight chunks
@@ -970,8 +978,11 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
     L.append(f"    const float* __restrict__ x, const float* __restrict__ sh, const {WT}* __restrict__ w,")
     L.append("    const int* __restrict__ sender, const int* __restrict__ receiver, int n_edges,")
     L.append("    const float* __restrict__ gagg, float inv_norm,")
-    L.append(f"    {WT}* __restrict__ gw, {WT}* __restrict__ gxe, const int* __restrict__ spos) {{")
+    L.append(f"    {WT}* __restrict__ gw, {WT}* __restrict__ gxe, const int* __restrict__ spos,")
+    L.append("    const int* __restrict__ wrow) {")
     L.append("  const int lane = threadIdx.x & 63;")
+    # wrow (optional): edge e reads weight row wrow[e] (shared rows); null = row e.  grad_w
+    # stays one row per edge, in edge order, either way
     if TP_BWD_XCD:
         # 1-D grid of 8 * nb8 * NBG blocks (eelg_capi.hip); block b runs on XCD b % 8, which
         # takes edge blocks [xcd * nb8, (xcd + 1) * nb8); surplus edge blocks exit below
@@ -1003,12 +1014,12 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
         g0_ = [f"g{p0.slot}_{k}" for k in range(2 * p0.l3 + 1)] + [f"w{p0.slot}"]
         L.append(f"  case {gi}: {{ // input block l1 = {l}")
 
-        def edge_loads(pref, sv, rv, ev):
+        def edge_loads(pref, sv, rv, ev, qv):
             """x / SH rows of an edge and its first path's grad_agg slice + weight"""
             out = [f"    {{ const float* __restrict__ xs = x + (size_t){sv} * {din};",
                    f"      const float* __restrict__ ye = sh + (size_t){ev} * {nshp};",
                    f"      const float* __restrict__ ge = gagg + (size_t){rv} * {dmid};",
-                   f"      const {WT}* __restrict__ we = w + (size_t){ev} * {wn} + {UC};"]
+                   f"      const {WT}* __restrict__ we = w + (size_t){qv} * {wn} + {UC};"]
             out += ["      " + ln for ln in vec_load([pref + v for v in xs_], "xs", f"{node_off[l]} + {UC} * {d}")]
             out += ["      " + ln for ln in sh_load(l2s, pref, "ye")]
             d3 = 2 * p0.l3 + 1
@@ -1018,15 +1029,16 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
             out.append("    }")
             return out
         L.append("    float " + ", ".join(xs_ + ys_ + g0_) + ";")
-        L.append("    int rcur = receiver[e0];")
-        L += edge_loads("", "sender[e0]", "rcur", "e0")
+        L.append("    int rcur = receiver[e0], qcur = wrow ? wrow[e0] : e0;")
+        L += edge_loads("", "sender[e0]", "rcur", "e0", "qcur")
         L.append("    for (int e = e0; e < e1; ++e) {")
         if EPH > 1:
             L.append("      const bool more = e + 1 < e1;")
             L.append("      const int sn = more ? sender[e + 1] : 0, rn = more ? receiver[e + 1] : 0;")
             L.append("      const int en = more ? e + 1 : e;")
+            L.append("      const int qn = more ? (wrow ? wrow[e + 1] : e + 1) : qcur;")
         L.append("      const float* __restrict__ ge = gagg + (size_t)rcur * " + str(dmid) + ";")
-        L.append(f"      const {WT}* __restrict__ we = w + (size_t)e * {wn} + {UC};")
+        L.append(f"      const {WT}* __restrict__ we = w + (size_t)qcur * {wn} + {UC};")
         L.append(f"      {WT}* __restrict__ gwe = gw + (size_t)e * {wn} + {UC};")
         L.append(f"      {WT}* __restrict__ gxo = gxe + (size_t)(spos ? spos[e] : e) * {din};")
         for i in range(d):
@@ -1058,7 +1070,7 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
                 # only the next path must have landed after this one; later paths stay in flight
                 nxt_regs = regs_of[pi + 1]
             elif EPH > 1:                    # next edge's loads in flight during the last path
-                L += ["  " + ln for ln in edge_loads("n", "sn", "rn", "en")]
+                L += ["  " + ln for ln in edge_loads("n", "sn", "rn", "en", "qn")]
                 nxt_regs = ["n" + v for v in xs_ + ys_ + g0_]
             else:
                 nxt_regs = []
@@ -1093,7 +1105,7 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
             L += ["      " + ln for ln in vec_store([f"gx{l}_{i}" for i in range(d)], "gxo", f"{node_off[l]} + {UC} * {d}",
                                                        nt=bool(TP_BWD_NT))]
         if EPH > 1:
-            L.append("      " + " ".join(f"{v} = n{v};" for v in xs_ + ys_ + g0_) + " rcur = rn;")
+            L.append("      " + " ".join(f"{v} = n{v};" for v in xs_ + ys_ + g0_) + " rcur = rn; qcur = qn;")
         L.append("    }")
         L.append("    break; }")
     L.append("  default: break;")

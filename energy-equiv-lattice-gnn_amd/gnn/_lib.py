@@ -38,6 +38,11 @@ _SIGS = {
     "eelg_tp_bwd_bf16": ([_I, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
     "eelg_tp_bwd_sorted": ([_I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
     "eelg_tp_bwd_sorted_bf16": ([_I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
+    # shared weight rows (one per strut): the per-edge row index after w
+    "eelg_tp_fwd_rows": ([_I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P], _I),
+    "eelg_tp_fwd_rows_bf16": ([_I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P], _I),
+    "eelg_tp_bwd_rows": ([_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
+    "eelg_tp_bwd_rows_bf16": ([_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
     "eelg_tp_bwd_sender": ([_I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
     "eelg_tp_bwd_sender_bf16": ([_I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P], _I),
     "eelg_tp_bwd_fused": ([_I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P], _I),
@@ -87,6 +92,7 @@ _SIGS = {
                        ctypes.c_longlong, _P], _I),
     "eelg_radial_fwd": ([_P, _I, _P, _P, _I, _P, _P, _P], _I),
     "eelg_radial_bwd_chain": ([_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "eelg_radial_bwd_chain_rows": ([_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "eelg_radial_bwd": ([_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     # geometry gradients
     "eelg_tp_bwd_sh": ([_I, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P], _I),

@@ -321,8 +321,19 @@ class TensorProductInteractionBlock(torch.nn.Module):
             self._tp_paths = cg.tp_paths(self._node_feats_irreps, self.edge_attrs_irreps, self._irreps_out)
         return ops.tp_linear_fusable(cfg, self.linear, self._tp_paths)
 
-    def radial_weights(self, edge_feats: torch.Tensor) -> torch.Tensor:
-        """``conv_tp_weights(edge_feats)`` (``gnn/blocks.py:590``): the per-edge TP weights."""
+    def strut_map(self, csr: ops.EdgeCSR, edge_feats, edge_attrs) -> Optional[ops.StrutMap]:
+        """the map to compute this block's radial weights on, one row per strut, or None for
+        per-edge weights: ``ops.strut_rows``, the one predicate ``GNN_Head`` and ``forward`` ask"""
+        if not self._radial_hip:
+            return None
+        return ops.strut_rows(csr, self.reduce, self.storage_dtype, self.conv_tp_weights,
+                              edge_feats, edge_attrs)
+
+    def radial_weights(self, edge_feats: torch.Tensor, smap: Optional[ops.StrutMap] = None):
+        """``conv_tp_weights(edge_feats)`` (``gnn/blocks.py:590``): the per-edge TP weights, or
+        with ``smap`` (from ``strut_map``) the ``ops.StrutWeights`` of one row per strut."""
+        if smap is not None:
+            return ops.radial_mlp_shared(edge_feats, self.conv_tp_weights, smap, self.storage_dtype)
         if self._radial_hip:
             return ops.radial_mlp(edge_feats, self.conv_tp_weights, self.storage_dtype)
         ops._require_device(edge_feats)
@@ -336,11 +347,12 @@ class TensorProductInteractionBlock(torch.nn.Module):
         csr, edge_attrs, edge_feats = as_csr(edge_index, node_feats.shape[0], edge_attrs, edge_feats)
         idx, info = self._config()
         w = tp_weights
+        smap = self.strut_map(csr, edge_feats, edge_attrs) if w is None else None
         if w is None and RADIAL_FIRST:
-            w = self.radial_weights(edge_feats)
+            w = self.radial_weights(edge_feats, smap)
         x = self.linear_up(node_feats, grad_mailbox=grad_mailbox)
         if w is None:
-            w = self.radial_weights(edge_feats)
+            w = self.radial_weights(edge_feats, smap)
         if self.reduce == "pna":
             # the unscaled per-edge messages, aggregated by PNASimple; no / agg_norm_const here
             m = ops.tp_interaction(x, edge_attrs, w, ops.per_edge_csr(csr), idx, info, 1.0)
@@ -391,7 +403,7 @@ class MACELayer(torch.nn.Module):
         into the product block's linear (``GNN_Head`` passes ``h`` for ``h + layer_i(h)``).
         ``live``: the product block's live outputs only (``EquivariantProductBlock.forward``)."""
         csr, edge_sh, edge_scalars = as_csr(edge_index, node_ft.shape[0], edge_sh, edge_scalars)
-        if tp_weights is not None and not isinstance(edge_index, ops.EdgeCSR):
+        if torch.is_tensor(tp_weights) and not isinstance(edge_index, ops.EdgeCSR):
             tp_weights = tp_weights[csr.perm]
         # the residual h is also linear_up's input: its two gradient contributions are summed
         # in linear_up's grad-x epilogue (o3.GradMailbox), not by autograd in a separate pass

@@ -260,7 +260,7 @@ class _CGCBase(torch.nn.Module):
     def _encode(self, batch, node_in):
         """(csr, node embedding, ef [E, 8] = [e5 | 1 | 0 | 0] in CSR order)"""
         from .model import EnergyEquivGNN
-        csr = EnergyEquivGNN.edge_graph(batch)
+        csr = EnergyEquivGNN.edge_graph(batch, strut=False)
         e5 = _edge_inputs(batch, csr)
         ef = torch.cat([e5, torch.ones_like(e5[:, :1]), torch.zeros_like(e5[:, :2])], dim=1).contiguous()
         return csr, self.node_ft_embedding(node_in), ef

@@ -170,7 +170,7 @@ class NNConvNet(torch.nn.Module):
     def forward(self, batch) -> Dict[str, torch.Tensor]:
         from .model import EnergyEquivGNN
         ops._require_device(batch.positions, batch.node_attrs)
-        csr = EnergyEquivGNN.edge_graph(batch)
+        csr = EnergyEquivGNN.edge_graph(batch, strut=False)
         edge_ft = _edge_inputs(batch, csr)
         h = self.node_ft_embedding(batch.node_attrs)
         for conv in self.conv_list:

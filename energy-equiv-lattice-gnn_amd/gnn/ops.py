@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -89,6 +90,11 @@ TP_BWF = os.environ.get("EELG_TP_BWF", "0") != "0"
 # Bitwise equal to the one-pass kernels; measured slower (r09g, same box, default 2205 / 2200
 # graphs/s: C 4 2171, C 8 2121, C 16 2007) -- each extra launch pair adds two kernel tails.
 TP_BWC = int(os.environ.get("EELG_TP_BWC", "0"))
+# one radial weight row per strut instead of one per directed edge (StrutMap, strut_rows): the
+# two directions of a strut have bitwise-equal edge features, so the radial MLP runs on the S
+# representative rows and tp_fwd / tp_bwd index them (eelg_tp_fwd_rows / eelg_tp_bwd_rows).
+# 0 keeps the per-edge path (A/B runs, tests)
+STRUT_WEIGHTS = os.environ.get("EELG_STRUT_WEIGHTS", "1") != "0"
 _SIDE: Dict[tuple, "torch.cuda.Stream"] = {}
 
 
@@ -130,12 +136,86 @@ def _i32(t: torch.Tensor) -> torch.Tensor:
 # edge graph in receiver-sorted order
 # ---------------------------------------------------------------------------
 @dataclass
+class StrutMap:
+    """Which receiver-sorted edges are the two directions of one strut (``build_strut_map``).
+
+    ``partner`` [E] int64: the edge with swapped endpoints, the exactly negated edge vector and
+    the bitwise-equal radius, or the edge itself when there is none (or no unique one); it defines
+    the map and nothing on the hot path reads it.  Paired edges share weight row ``row[e]``; every
+    other edge has a row of its own.  ``row`` [E] int32 is the index ``eelg_tp_fwd_rows`` /
+    ``eelg_tp_bwd_rows`` / ``eelg_radial_bwd_chain_rows`` take.  ``rep`` [S] int64: the
+    representative (first) edge of each row, ascending."""
+    partner: torch.Tensor
+    row: torch.Tensor
+    rep: torch.Tensor
+    n_rows: int
+
+    @property
+    def num_edges(self) -> int:
+        return int(self.row.shape[0])
+
+    def rep_rows(self, feats: torch.Tensor) -> torch.Tensor:
+        """``feats[rep]`` [S, n_feat], gathered once per feature tensor: every layer's radial MLP
+        of a forward reads the same rows.  The memo holds ``feats`` weakly and its version."""
+        memo = getattr(self, "_rep_rows", None)
+        if memo is not None and memo[0]() is feats and memo[1] == feats._version:
+            return memo[2]
+        rows = feats[self.rep]
+        self._rep_rows = (weakref.ref(feats), feats._version, rows)
+        return rows
+
+
+def _key_bits(v: torch.Tensor) -> torch.Tensor:
+    """fp32 -> int64 bit patterns with -0.0 folded into +0.0 (``x + 0.0``)"""
+    return (v + 0.0).contiguous().view(torch.int32).to(torch.int64)
+
+
+def build_strut_map(pos: torch.Tensor, sender: torch.Tensor, receiver: torch.Tensor,
+                    shifts_sorted: torch.Tensor, radius_sorted: torch.Tensor) -> StrutMap:
+    """``StrutMap`` of a batch (plain torch, any device; one host sync for the row count).
+
+    Edge e's key is (sender, receiver, edge vector, radius) with the vector formed as
+    ``eelg_edge_embed`` forms it, ``(pos[r] - pos[s]) + shift`` in fp32; its partner is the
+    edge whose key is (receiver, sender, -vector, radius).  The negation is exact in IEEE
+    arithmetic, so partners have bitwise-equal lengths and hence bitwise-equal edge features.
+    Several images of a strut between one node pair differ in their vectors and pair up
+    separately.  An edge whose key, or whose partner's key, occurs more than once stays alone."""
+    e = int(sender.shape[0])
+    dev = sender.device
+    ar = torch.arange(e, device=dev)
+    if e == 0:
+        z = torch.zeros(0, device=dev, dtype=torch.int64)
+        return StrutMap(z, z.to(torch.int32), z, 0)
+    s, r = sender.long(), receiver.long()
+    pos = pos.detach().to(torch.float32)
+    vec = (pos[r] - pos[s]) + shifts_sorted.detach().to(torch.float32)
+    rad = _key_bits(radius_sorted.detach().to(torch.float32).reshape(e, 1))
+    fwd = torch.cat([s[:, None], r[:, None], _key_bits(vec), rad], 1)
+    rev = torch.cat([r[:, None], s[:, None], _key_bits(-vec), rad], 1)
+    _, inv = torch.unique(torch.cat([fwd, rev]), dim=0, return_inverse=True)
+    kf, kr = inv[:e], inv[e:]
+    nk = int(inv.max()) + 1
+    cnt = torch.zeros(nk, device=dev, dtype=torch.int64).index_add_(0, kf, torch.ones_like(kf))
+    owner = torch.full((nk,), -1, device=dev, dtype=torch.int64)
+    owner[kf] = ar                                  # read only where the key has one owner
+    cand = owner[kr]
+    ok = (cnt[kf] == 1) & (cnt[kr] == 1) & (cand >= 0)
+    partner = torch.where(ok, cand, ar)
+    is_rep = partner >= ar
+    rep = torch.nonzero(is_rep).reshape(-1)
+    row_of = torch.cumsum(is_rep.to(torch.int64), 0) - 1
+    row = row_of[torch.minimum(partner, ar)].to(torch.int32)
+    return StrutMap(partner, row.contiguous(), rep, int(rep.shape[0]))
+
+
+@dataclass
 class EdgeCSR:
     """Edges in receiver-sorted order.
 
     ``perm`` maps the sorted order back to the caller's edge order
     (``sorted_edge_j = original_edge[perm[j]]``).  ``rowptr`` is the receiver
-    CSR; ``sperm`` / ``srowptr`` group the sorted edges by sender."""
+    CSR; ``sperm`` / ``srowptr`` group the sorted edges by sender.  ``strut``: the batch's
+    ``StrutMap`` where ``EnergyEquivGNN.edge_graph`` built one."""
     perm: torch.Tensor
     sender: torch.Tensor
     receiver: torch.Tensor
@@ -143,6 +223,7 @@ class EdgeCSR:
     sperm: torch.Tensor
     srowptr: torch.Tensor
     num_nodes: int
+    strut: Optional[StrutMap] = None
 
     @property
     def num_edges(self) -> int:
@@ -639,14 +720,118 @@ def _tp_bwd_sh(ctx, x, w, g):
     return gsh[:, :nsh]
 
 
+class StrutWeights:
+    """The radial weights of a layer as one row per strut (``radial_mlp_shared``): ``w`` [S, W]
+    (no autograd edge), the ``smap`` that indexes it, and the hand-over of its gradient.  The
+    per-edge ``grad_w`` [E, W] that ``eelg_tp_bwd_rows`` writes is not of ``w``'s shape (and summing
+    it per pair would be a new pass over an edge-sized tensor), so it cannot travel as ``w``'s
+    autograd gradient: the TP backward leaves it in ``box.gw`` and returns
+    a gradient for the one-element ``token`` instead, which is the radial MLP's differentiable
+    output and so triggers (and orders, across streams) the MLP backward that takes ``gw``.
+
+    Limits of this hand-over: one ``StrutWeights`` feeds exactly one ``tp_interaction`` and one
+    backward pass (a second backward over a retained graph raises in the MLP's backward, which
+    finds the box empty); with every MLP parameter frozen the token needs no gradient and the TP
+    backward keeps nothing in the box."""
+
+    def __init__(self, w, smap: StrutMap, token, box: "_GradBox"):
+        self.w, self.smap, self.token, self.box = w, smap, token, box
+
+
+class _GradBox:
+    """where the TP backward leaves the per-edge ``grad_w`` for the radial MLP's backward (the
+    two autograd nodes hold the box, not each other's tensors)"""
+    gw: Optional[torch.Tensor] = None
+
+
+_ZERO1: Dict[str, torch.Tensor] = {}
+
+
+def _zero1(device) -> torch.Tensor:
+    """a constant one-element zero on ``device`` (the token's gradient; never written)"""
+    key = str(device)
+    if key not in _ZERO1:
+        _ZERO1[key] = torch.zeros(1, device=device, dtype=torch.float32)
+    return _ZERO1[key]
+
+
+class _TPInteractionRows(torch.autograd.Function):
+    """``_TPInteraction`` over shared weight rows (``StrutWeights``): same kernels with the
+    per-edge row index, bitwise the results of the expanded per-edge ``w[row]``."""
+
+    @staticmethod
+    def forward(ctx, x, sh, token, sw: StrutWeights, csr: EdgeCSR, cfg: int, info, inv_norm: float):
+        agg, x, sh, w = _tp_fwd(x, sh, sw.w, csr, cfg, info, inv_norm, sw.smap)
+        ctx.save_for_backward(x, sh, w)
+        ctx.smap, ctx.box = sw.smap, sw.box
+        ctx.csr, ctx.cfg, ctx.info, ctx.inv_norm = csr, cfg, info, inv_norm
+        return agg
+
+    @staticmethod
+    def backward(ctx, g):
+        x, sh, w = ctx.saved_tensors
+        csr, info, smap = ctx.csr, ctx.info, ctx.smap
+        g = _f32(g)
+        e = csr.num_edges
+        gw = torch.empty(e, info["wn"], device=x.device, dtype=w.dtype)    # per edge, as ever
+        gxe = torch.empty(e, info["din"], device=x.device, dtype=w.dtype)
+        spos = csr.sender_pos() if TP_BWD_SPOS else None
+        lib = _lib.load()
+        bwd = lib.eelg_tp_bwd_rows_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_rows
+        tok = TIMER.start(f"tp_bwd[din={info['din']}]")
+        _lib.check(bwd(ctx.cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(smap.row),
+                       _lib.ptr(csr.sender), _lib.ptr(csr.receiver), _lib.ptr(spos), e, _lib.ptr(g),
+                       float(ctx.inv_norm), _lib.ptr(gw), _lib.ptr(gxe), _lib.stream(gxe)), "tp_bwd")
+        TIMER.stop(tok)
+        if ctx.needs_input_grad[2]:                 # else nobody will take it: keep nothing alive
+            ctx.box.gw = gw
+        gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes,
+                             idx=None if spos is not None else csr.sperm)
+        return gx, None, (_zero1(x.device) if ctx.needs_input_grad[2] else None), None, None, None, None, None
+
+
 def tp_interaction(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: float):
+    """``w``: the per-edge weights [E, W], or ``StrutWeights`` (one row per strut)"""
+    if isinstance(w, StrutWeights):
+        _require_device(x, sh, w.w)
+        return _TPInteractionRows.apply(x, sh, w.token, w, csr, cfg, info, inv_norm)
     _require_device(x, sh, w)
     return _TPInteraction.apply(x, sh, w, csr, cfg, info, inv_norm)
 
 
-def _tp_fwd(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: float):
+def strut_rows(csr: EdgeCSR, reduce: str, storage, mlp: torch.nn.Sequential,
+               *edge_tensors) -> Optional[StrutMap]:
+    """THE predicate of the shared-row path: the ``StrutMap`` to compute a layer's radial
+    weights on (``radial_mlp_shared``), or None for per-edge weights.  Shared rows serve the
+    default training path only: the switch on, a map on the CSR that pairs some edges, the
+    fused 'sum' / 'add' / 'mean' interaction with the per-edge backward (none of EELG_TP_BWF /
+    EELG_TP_BWC / EELG_TP_BWD_SENDER), no geometry gradients (``edge_tensors``: the SH and the
+    edge features), and the chain form of the MLP backward (hidden 64, one launch range)."""
+    smap = csr.strut
+    if not STRUT_WEIGHTS or smap is None or smap.num_edges != csr.num_edges:
+        return None
+    if smap.n_rows == 0 or smap.n_rows >= csr.num_edges:       # no pair: nothing to share
+        return None
+    if reduce not in ("sum", "add", "mean") or TP_BWF or TP_BWC > 1:
+        return None
+    if TP_BWD_SENDER or (TP_BWD_SENDER is None and storage == torch.bfloat16):
+        return None
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in edge_tensors):
+        return None
+    lins = [m for m in mlp if isinstance(m, torch.nn.Linear)]
+    if not RADIAL_CHAIN or any(m.out_features != 64 for m in lins[:-1]):
+        return None
+    n_out = -(-lins[-1].out_features // 8) * 8
+    es = 2 if storage == torch.bfloat16 else 4
+    if len(_radial_chunks(csr.num_edges, n_out, es, 64, len(lins) - 1)) != 1:
+        return None
+    return smap
+
+
+def _tp_fwd(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: float,
+            smap: Optional[StrutMap] = None):
     """tp_fwd launch with the input checks of ``_TPInteraction``; returns (agg, x, sh, w) with
-    the operands as the kernels read them"""
+    the operands as the kernels read them.  ``smap``: ``w`` holds its ``n_rows`` shared rows."""
     bf = w.dtype == torch.bfloat16
     x = _a16(x)
     if bf:
@@ -661,14 +846,18 @@ def _tp_fwd(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: fl
     if x.shape[1] != info["din"] or sh.shape[1] != info["nsh"] or w.shape[1] != info["wn"]:
         raise ValueError(f"shape mismatch: x {tuple(x.shape)} sh {tuple(sh.shape)} "
                          f"w {tuple(w.shape)} vs config {info}")
-    if sh.shape[0] != csr.num_edges or w.shape[0] != csr.num_edges or n != csr.num_nodes:
+    w_rows = csr.num_edges if smap is None else smap.n_rows
+    if sh.shape[0] != csr.num_edges or w.shape[0] != w_rows or n != csr.num_nodes:
         raise ValueError("edge/node counts do not match the CSR")
+    if smap is not None and smap.num_edges != csr.num_edges:
+        raise ValueError("the strut map is not of this CSR")
     n_out = csr.rowptr.shape[0] - 1
     agg = torch.empty(n_out, info["dmid"], device=x.device, dtype=torch.float32)
     lib = _lib.load()
     tok = TIMER.start(f"tp_fwd[din={info['din']}]")
-    fwd = lib.eelg_tp_fwd_bf16 if bf else lib.eelg_tp_fwd
-    _lib.check(fwd(cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(csr.sender),
+    fwd = lib.eelg_tp_fwd_rows_bf16 if bf else lib.eelg_tp_fwd_rows
+    _lib.check(fwd(cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w),
+                   _lib.ptr(smap.row) if smap is not None else None, _lib.ptr(csr.sender),
                    _lib.ptr(csr.rowptr), n_out, float(inv_norm), _lib.ptr(agg), _lib.stream(agg)),
                "tp_fwd")
     TIMER.stop(tok)
@@ -1303,10 +1492,91 @@ def _radial_bwd_x(grad_h, d, z, out) -> None:
     TIMER.stop(tok)
 
 
-def radial_mlp(feats: torch.Tensor, mlp: torch.nn.Sequential,
-               out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """Apply ``mlp`` = [Linear(bias), SiLU]*k + [Linear(no bias)] with the fused backward.
-    ``out_dtype`` bf16: the [E, W] output (the TP weights) is stored in bf16."""
+class _RadialMLPShared(torch.autograd.Function):
+    """``_RadialMLP`` on the ``S`` representative feature rows of a ``StrutMap`` (hidden 64, the
+    chain backward, one launch range: ``strut_rows``).  Outputs the ``StrutWeights``' ``w`` [S, W]
+    (non-differentiable) and its token; the backward takes the per-edge ``grad_w`` [E, W] from
+    the ``StrutWeights`` and runs ``_RadialMLP``'s chain backward over the E edges in edge order,
+    the kernels reading edge e's saved pre-activations at row ``smap.row[e]``
+    (``eelg_radial_bwd_chain_rows``).  Every per-edge quantity is bitwise the per-edge MLP's and
+    every sum keeps its order, so the parameter gradients are bitwise those of ``_RadialMLP``."""
+
+    @staticmethod
+    def forward(ctx, feats, out_dtype, smap: StrutMap, box: _GradBox, *params):
+        _require_device(feats)
+        feats = _f32(feats)
+        feats_s = smap.rep_rows(feats)               # [S, n_feat]: the only new pass
+        params = tuple(_f32(p) for p in params)
+        s_rows, nf = feats_s.shape
+        d = _radial_desc(params, nf)
+        wo = params[-1]
+        n_out = d.n_out
+        wp = -(-n_out // 8) * 8
+        if wp != n_out:
+            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
+            d.n_out = wp
+        if d.hidden != 64 or any(p.shape[0] != 64 for p in params[:-1]) or wo.shape[1] != 64:
+            raise ValueError("radial MLP on shared rows: hidden width 64 only")
+        out = torch.empty(s_rows, wp, device=feats.device, dtype=out_dtype)
+        z = torch.empty(d.n_hidden, s_rows, d.hidden, device=feats.device, dtype=torch.float32)
+        _lib.check(_lib.load().eelg_radial_fwd(
+            _lib.ptr(feats_s), s_rows, ctypes.byref(d), _lib.ptr(split_bf16x3(wo)),
+            int(out_dtype == torch.bfloat16), _lib.ptr(z), _lib.ptr(out), _lib.stream(feats)),
+            "radial_fwd")
+        token = torch.empty(1, device=feats.device, dtype=torch.float32)
+        w = out if wp == n_out else out[:, :n_out].contiguous()
+        ctx.box, ctx.smap = box, smap
+        ctx.save_for_backward(feats, z, *params)
+        ctx.mark_non_differentiable(w)
+        ctx.set_materialize_grads(False)             # no [S, W] zeros for w's absent gradient
+        return w, token
+
+    @staticmethod
+    def backward(ctx, _gw_unused, _gtoken):
+        from . import dense
+        feats, z, *params = ctx.saved_tensors
+        g, ctx.box.gw = ctx.box.gw, None
+        if g is None:
+            raise RuntimeError("radial MLP on shared rows: no weight gradient was handed over "
+                               "(the interaction's backward has not run, or ran twice)")
+        g.record_stream(torch.cuda.current_stream(g.device))     # made on the TP's stream
+        smap = ctx.smap
+        e, nf = feats.shape
+        d = _radial_desc(params, nf)
+        n_out = d.n_out
+        wp = -(-n_out // 8) * 8
+        wo = params[-1]
+        if wp != n_out:
+            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
+            g = torch.cat([g, g.new_zeros(g.shape[0], wp - n_out)], 1)
+            d.n_out = wp
+        lib = _lib.load()
+        wot_parts = split_bf16x3(wo.t().contiguous())
+        h, nh = d.hidden, d.n_hidden
+        dev = g.device
+        npart, ns = ctypes.c_int(), ctypes.c_int()
+        _lib.check(lib.eelg_radial_plan(e, d.n_out, ctypes.byref(npart), ctypes.byref(ns)), "radial_plan")
+        part_wo = torch.empty(ns.value, d.n_out, h, device=dev, dtype=torch.float32)
+        grad_h = torch.empty(e, h, device=dev, dtype=torch.float32)
+        gz = torch.empty(nh, e, h, device=dev, dtype=torch.float32)
+        hin = torch.empty(max(nh - 1, 1), e, h, device=dev, dtype=torch.float32)
+        zlast = torch.empty(e, h, device=dev, dtype=torch.float32)
+        _lib.check(lib.eelg_radial_bwd_chain_rows(
+            _lib.ptr(g), int(g.dtype == torch.bfloat16), e, _lib.ptr(smap.row), smap.n_rows,
+            ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z), _lib.ptr(grad_h), _lib.ptr(gz),
+            _lib.ptr(hin), _lib.ptr(zlast), _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd_chain_rows")
+        grads = []
+        for n in range(nh):                           # as _RadialMLP._backward_chain, one range
+            x_n = feats if n == 0 else hin[n - 1]
+            grads.append(dense.linear_bwd_w(x_n, gz[n]).view_as(params[2 * n]))
+            grads.append(sum_rows(gz[n]).view_as(params[2 * n + 1]))
+        gwo = sum_rows(part_wo)
+        grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
+        return (None, None, None, None, *grads)
+
+
+def _radial_params(mlp: torch.nn.Sequential) -> list:
+    """the parameters of ``mlp`` = [Linear(bias), SiLU]*k + [Linear(no bias)] in kernel order"""
     mods = list(mlp)
     params = []
     for i, mod in enumerate(mods):
@@ -1319,6 +1589,27 @@ def radial_mlp(feats: torch.Tensor, mlp: torch.nn.Sequential,
                 params.append(mod.bias)
         elif not isinstance(mod, torch.nn.SiLU):
             raise ValueError(f"radial MLP: unsupported module {type(mod).__name__}")
+    return params
+
+
+def radial_mlp_shared(feats: torch.Tensor, mlp: torch.nn.Sequential, smap: StrutMap,
+                      out_dtype: torch.dtype = torch.float32) -> StrutWeights:
+    """``radial_mlp`` computed once per row of ``smap`` (``strut_rows`` decides where this
+    applies): the ``StrutWeights`` that ``tp_interaction`` takes in place of [E, W] weights."""
+    if smap.n_rows == 0:
+        raise ValueError("radial MLP on shared rows: the map has no rows")
+    box = _GradBox()
+    tok = TIMER.start("radial_mlp_fwd")
+    w, token = _RadialMLPShared.apply(_f32(feats), out_dtype, smap, box, *_radial_params(mlp))
+    TIMER.stop(tok)
+    return StrutWeights(w, smap, token, box)
+
+
+def radial_mlp(feats: torch.Tensor, mlp: torch.nn.Sequential,
+               out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Apply ``mlp`` = [Linear(bias), SiLU]*k + [Linear(no bias)] with the fused backward.
+    ``out_dtype`` bf16: the [E, W] output (the TP weights) is stored in bf16."""
+    params = _radial_params(mlp)
     tok = TIMER.start("radial_mlp_fwd")
     out = _RadialMLP.apply(_f32(feats), out_dtype, *params)
     TIMER.stop(tok)

@@ -109,6 +109,27 @@ int eelg_tp_bwd_sorted_bf16(int cfg, const float* x, const float* sh, const void
                             const float* grad_agg, float inv_norm, void* grad_w, void* gxe,
                             void* stream);
 
+/* eelg_tp_fwd / eelg_tp_bwd_sorted (and their _bf16 forms) over SHARED weight rows: the two
+ * directions of a strut have equal edge features, hence equal rows of conv_tp_weights
+ * (gnn/blocks.py:590), so w holds S <= E rows and wrow[E] (int32) names each edge's row in
+ * [0, S).  Forward and backward read w[wrow[e]]; grad_w stays [E, weight_numel], one row per
+ * edge in edge order, bitwise what the plain entry points give for the expanded w[wrow].
+ * wrow == NULL: every edge its own row, exactly eelg_tp_fwd / eelg_tp_bwd_sorted.
+ * Indices are not range-checked: 0 <= wrow[e] < S is the caller's contract. */
+int eelg_tp_fwd_rows(int cfg, const float* x, const float* sh, const float* w, const int* wrow,
+                     const int* sender, const int* rowptr, int n_nodes, float inv_norm, float* agg,
+                     void* stream);
+int eelg_tp_fwd_rows_bf16(int cfg, const float* x, const float* sh, const void* w, const int* wrow,
+                          const int* sender, const int* rowptr, int n_nodes, float inv_norm,
+                          float* agg, void* stream);
+int eelg_tp_bwd_rows(int cfg, const float* x, const float* sh, const float* w, const int* wrow,
+                     const int* sender, const int* receiver, const int* spos, int n_edges,
+                     const float* grad_agg, float inv_norm, float* grad_w, float* gxe, void* stream);
+int eelg_tp_bwd_rows_bf16(int cfg, const float* x, const float* sh, const void* w, const int* wrow,
+                          const int* sender, const int* receiver, const int* spos, int n_edges,
+                          const float* grad_agg, float inv_norm, void* grad_w, void* gxe,
+                          void* stream);
+
 /* Backward of eelg_tp_fwd in sender order: one pass over the sender CSR (srowptr [N+1],
  * sperm [E] = edge ids sorted by sender) that writes grad_w[E, weight_numel] at each edge's
  * row and grad_x[N, din] summed per sender in registers -- eelg_tp_bwd + the sender
@@ -490,6 +511,17 @@ int eelg_radial_bwd(const void* grad_w, int grad_bf16, int n_edges, const eelg_r
 int eelg_radial_bwd_chain(const void* grad_w, int grad_bf16, int n_edges, const eelg_radial_desc* d,
                           const void* wot_parts, const float* zsave, float* grad_h, float* gz,
                           float* hin, float* part_wo, void* stream);
+/* eelg_radial_bwd_chain for an MLP that ran on n_rows <= E shared rows (eelg_radial_fwd over
+ * the representative feature rows; zsave [n_hidden, n_rows, 64]): zrow[E] (int32, 0 <= zrow[e] <
+ * n_rows, not range-checked) names the row of edge e.  grad_w, grad_h, gz and hin are per edge,
+ * in edge order, as in eelg_radial_bwd_chain, and every result is bitwise what that entry
+ * gives for the expanded zsave[:, zrow].  zlast [E, 64] is workspace: the chain kernel leaves the
+ * last layer's pre-activations there per edge for the W_o gradient to stream.  No [E, n_out]
+ * tensor is expanded or summed per pair, and grad_w is read twice as there. */
+int eelg_radial_bwd_chain_rows(const void* grad_w, int grad_bf16, int n_edges, const int* zrow,
+                               int n_rows, const eelg_radial_desc* d, const void* wot_parts,
+                               const float* zsave, float* grad_h, float* gz, float* hin,
+                               float* zlast, float* part_wo, void* stream);
 
 /* ---- Geometry gradients: d stiffness / d (positions, shifts, strut radii) -------------------
  * The reference model is plain differentiable torch, so autograd through its embedding

@@ -145,6 +145,24 @@ def main():
                                        ops._lib.stream(x)), "tp_bwd")
     bwd_bytes = 4 * (n * 800 + e * 25 + 2 * e * info["wn"] + 2 * e + e * 800 + n * info["dmid"])
     rec("tp_bwd (B)", timeit_if("tp_bwd (B)", tpb, args.reps), bwd_bytes, 2 * tp_flops)
+    # one weight row per strut (ops.StrutMap): the same kernels with the per-edge row index over
+    # S = E / 2 shared rows (grad_w stays per edge); bytes count each shared row once
+    smap = ops.build_strut_map(b.positions, csr.sender, csr.receiver, b.shifts[csr.perm],
+                               b.edge_attr[csr.perm].reshape(-1))
+    s_rows = smap.n_rows
+    w_s = torch.randn(s_rows, info["wn"], device=dev)
+    sw = ops.StrutWeights(w_s, smap, torch.zeros(1, device=dev), ops._GradBox())
+    rec("tp_fwd (B) shared rows",
+        timeit_if("tp_fwd (B) shared rows", lambda: ops.tp_interaction(x, sh, sw, csr, idx, info, 0.25), args.reps),
+        tp_bytes - 4 * (e - s_rows) * info["wn"] + 4 * e, tp_flops)
+
+    def tpb_rows():
+        ops._lib.check(lib.eelg_tp_bwd_rows(idx, ops._lib.ptr(x), ops._lib.ptr(sh), ops._lib.ptr(w_s),
+                                            ops._lib.ptr(smap.row), ops._lib.ptr(csr.sender),
+                                            ops._lib.ptr(csr.receiver), None, e, ops._lib.ptr(g), 0.25,
+                                            ops._lib.ptr(gw), ops._lib.ptr(gxe), ops._lib.stream(x)), "tp_bwd")
+    rec("tp_bwd (B) shared rows", timeit_if("tp_bwd (B) shared rows", tpb_rows, args.reps),
+        bwd_bytes - 4 * (e - s_rows) * info["wn"] + 4 * e, 2 * tp_flops)
     # geometry gradients: the interaction's SH gradient reads the rows tp_bwd reads (without the
     # SH) and writes one padded 28-float row per edge instead of grad_w + gxe
     gsh = torch.empty(e, 28, device=dev)
@@ -277,6 +295,18 @@ def main():
         out = ops.radial_mlp(efn, mlp)
         out.backward(torch.ones_like(out))
     rec("radial fwd+bwd (HIP)", timeit_if("radial fwd+bwd (HIP)", radfb, args.reps), None, 3 * rad_fl)
+    # the MLP on the S representative rows; its backward takes the per-edge grad_w [E, wn]
+    rec("radial fwd (HIP) shared rows",
+        timeit_if("radial fwd (HIP) shared rows", lambda: ops.radial_mlp_shared(efn, mlp, smap), args.reps),
+        None, rad_fl * s_rows // e)
+    gw_ones = torch.ones(e, info["wn"], device=dev)
+
+    def radfb_rows():
+        out = ops.radial_mlp_shared(efn, mlp, smap)
+        out.box.gw = gw_ones
+        out.token.backward(torch.zeros(1, device=dev))
+    rec("radial fwd+bwd (HIP) shared rows", timeit_if("radial fwd+bwd (HIP) shared rows", radfb_rows, args.reps),
+        None, rad_fl * s_rows // e + 2 * rad_fl)
     # geometry gradients: the MLP's input gradient from grad_h and the saved pre-activations
     zs = torch.randn(2, e, 64, device=dev)
     gh = torch.randn(e, 64, device=dev)

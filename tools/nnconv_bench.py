@@ -101,7 +101,7 @@ def main():
     plist = list(model.parameters())
     opt = torch.optim.AdamW(plist, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, amsgrad=True,
                             weight_decay=1e-8, fused=True)
-    csr = EnergyEquivGNN.edge_graph(batch)
+    csr = EnergyEquivGNN.edge_graph(batch, strut=False)
 
     def step(fused):
         nnconv.NNCONV_FUSED = fused

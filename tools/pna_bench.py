@@ -168,7 +168,7 @@ def main():
         del models, opts
         torch.cuda.empty_cache()
     if args.kernels:
-        csr = EnergyEquivGNN.edge_graph(batch)
+        csr = EnergyEquivGNN.edge_graph(batch, strut=False)
         print(json.dumps({"kernels": kernel_times(csr, 7360, 10, 3)}), flush=True)
 
 

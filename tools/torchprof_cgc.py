@@ -33,7 +33,7 @@ def main():
     iu = torch.triu_indices(6, 6)
     target = batch.stiffness if modified else batch.stiffness[:, iu[0], iu[1]]
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3, amsgrad=True, weight_decay=1e-8, fused=True)
-    EnergyEquivGNN.edge_graph(batch)
+    EnergyEquivGNN.edge_graph(batch, strut=False)
 
     def step():
         opt.zero_grad(set_to_none=True)
