@@ -14,6 +14,8 @@ from .design import stiffness_sensitivity  # noqa: F401
 from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
 from .metrics import (METRIC_COLUMNS, ErrorTable, aggr_errors, evaluate, metric_directions,  # noqa: F401
                       obtain_errors, stiffness_metrics, validation_metrics)
+from .optim import FlatAdamW  # noqa: F401
+from .trainer import Callback, EarlyStopping, ModelCheckpoint, Trainer  # noqa: F401
 
 __all__ = ["GLAMM_Dataset", "EnergyEquivGNN"]
 classes = __all__

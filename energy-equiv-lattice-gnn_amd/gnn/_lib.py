@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("EELG_LIB") or os.path.join(os.path.dirname(os.path.ab
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_D = ctypes.c_double
+_LL = ctypes.c_longlong
 
 _SIGS = {
     "eelg_version": ([], ctypes.c_char_p),
@@ -104,6 +106,11 @@ _SIGS = {
     "eelg_mandel_rotate": ([_P, _I, _P, _P, _I, _P, _P], _I),
     # validation / test metrics of predicted stiffness matrices
     "eelg_stiffness_metrics": ([_P, _P, _P, _I, _I, _F, _P, _P], _I),
+    # the tail of the training step: loss + gradient, gradient norm partials, clip + AdamW
+    "eelg_stiffness_loss": ([_P, _P, _I, _I, _F, _P, _P, _P], _I),
+    "eelg_sqnorm_parts": ([_LL], _I),
+    "eelg_grad_sqnorm": ([_P, _LL, _P, _P], _I),
+    "eelg_adamw_flat": ([_P, _P, _P, _P, _P, _LL, _P, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P], _I),
 }
 
 LIN_MAXSRC, LIN_MAXSLOT, LINW_MAXINS = 4, 8, 8
@@ -134,6 +141,7 @@ class LinWDesc(ctypes.Structure):
 
 BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
 METRICS_COLS = 16        # include/eelg.h EELG_METRICS_COLS
+OPTIM_STATE_COLS = 4     # include/eelg.h EELG_OPTIM_STATE_COLS
 
 
 class BatchSrc(ctypes.Structure):

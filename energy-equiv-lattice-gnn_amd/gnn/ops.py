@@ -1680,3 +1680,59 @@ class _SymConCoef(torch.autograd.Function):
 def symcon_coefficients(w: torch.Tensor, sp: SparseRows, ld: Optional[int] = None) -> torch.Tensor:
     """[mul, ld] coefficients (``ld``: the contraction config's ``coef_ld``; default nterms)."""
     return _SymConCoef.apply(w, sp, sp.shape[0] if ld is None else ld)
+
+
+# ---------------------------------------------------------------------------------------------
+# the training loss and its gradient in one launch (csrc/eelg_optim.hip)
+LOSS_FUSED = os.environ.get("EELG_LOSS_FUSED", "1") != "0"
+
+
+class _StiffnessLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, grad_scale: float):
+        _require_device(pred, target)
+        nb = int(target.shape[0])
+        p2 = _f32(pred).reshape(nb, -1)
+        t2 = _f32(target).reshape(nb, -1)
+        n = int(t2.shape[1])
+        out = torch.empty(2, device=pred.device, dtype=torch.float32)
+        grad = torch.empty_like(p2)
+        with torch.cuda.device(pred.device):
+            tok = TIMER.start("stiffness_loss")
+            _lib.check(_lib.load().eelg_stiffness_loss(_lib.ptr(p2), _lib.ptr(t2), nb, n, float(grad_scale),
+                                                       _lib.ptr(out), _lib.ptr(grad), _lib.stream(pred)),
+                       "stiffness_loss")
+            TIMER.stop(tok)
+        ctx.save_for_backward(grad)
+        ctx.shape = pred.shape
+        loss, mean = out[0], out[1]
+        ctx.mark_non_differentiable(mean)
+        return loss, mean
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mean):
+        (grad,) = ctx.saved_tensors
+        return (grad * g_loss).view(ctx.shape), None, None
+
+
+def stiffness_loss_fused(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0):
+    """``(loss, stiffness_loss_mean)`` of ``LightningWrappedModel.training_step``
+    (``scripts/train_utils.py:52-60``) as 0-dim device tensors: ``loss = 100 * mean_b(mean_ij
+    (C - C^)^2 / mean_ij C^2)``, ``stiffness_loss_mean = mean_b mean_ij (C - C^)^2`` (logged only,
+    no gradient).  ``pred`` / ``target``: ``[B, 6, 6]`` or ``[B, 21]``.
+
+    ``loss`` carries its unscaled value; its BACKWARD gives ``grad_scale`` times the gradient
+    (``grad_scale = 1 / accumulate_grad_batches``: the division Lightning applies between
+    ``training_step`` and ``backward`` is folded into the launch, and the backward is one
+    elementwise multiply by the incoming scalar).  On CPU tensors, or with ``EELG_LOSS_FUSED=0``,
+    the composed torch form with the same contract."""
+    if tuple(pred.shape) != tuple(target.shape) or pred.dim() < 2:
+        raise ValueError(f"stiffness_loss_fused: pred {tuple(pred.shape)}, target {tuple(target.shape)}")
+    if LOSS_FUSED and pred.is_cuda:
+        return _StiffnessLoss.apply(pred, target.detach(), float(grad_scale))
+    dims = tuple(range(1, target.dim()))
+    per_graph = torch.nn.functional.mse_loss(pred, target, reduction="none").mean(dim=dims)
+    loss = 100 * (per_graph / target.pow(2).mean(dim=dims)).mean()
+    if grad_scale != 1.0:     # value unscaled, gradient scaled
+        loss = loss.detach() + (loss - loss.detach()) * grad_scale
+    return loss, per_graph.detach().mean()

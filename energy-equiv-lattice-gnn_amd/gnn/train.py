@@ -1,5 +1,5 @@
 """Training-step semantics of ``LightningWrappedModel`` (``scripts/train_utils.py:26-64``)
-without the Lightning runtime (not installed; its control plane is out of scope).
+without the Lightning runtime (not installed; the loop around these steps is ``gnn.trainer``).
 
 ``training_step`` computes the reference loss
 ``100 * mean_b( mean_ij (C - C^)^2 / mean_ij C^2 )``; ``configure_optimizers``
@@ -41,6 +41,15 @@ class LightningWrappedModel(torch.nn.Module):
 
     def training_step(self, batch, batch_idx: int = 0) -> torch.Tensor:
         out = self.model(batch)
+        if getattr(self.params, "fused_loss", False):
+            # one launch for the loss and its gradient (ops.stiffness_loss_fused); the backward of
+            # the returned loss is scaled by self.loss_grad_scale (1 / accumulate_grad_batches,
+            # set by the loop; default 1), its value is not.  Both logged values stay on the device.
+            from .ops import stiffness_loss_fused
+            loss, mean = stiffness_loss_fused(out["stiffness"], batch["stiffness"],
+                                              getattr(self, "loss_grad_scale", 1.0))
+            self.train_metrics = {"loss": loss.detach(), "stiffness_loss": mean}
+            return loss
         return stiffness_loss(out["stiffness"], batch["stiffness"])
 
     def validation_step(self, batch, batch_idx: int = 0, directions=None) -> torch.Tensor:

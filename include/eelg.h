@@ -669,6 +669,52 @@ int eelg_mandel_rotate(const float* src, int n_src, const int* sel, const float*
 int eelg_stiffness_metrics(const float* pred, const float* target, const float* dirs, int n_graphs,
                            int n_dirs, float scale, float* out, void* stream);
 
+/* ---- The tail of the training step: loss, gradient norm, clip + AdamW --------------------------
+ * (csrc/eelg_optim.hip; per-element arithmetic in csrc/eelg_adamw.h)
+ *
+ * eelg_stiffness_loss: LightningWrappedModel.training_step's loss (scripts/train_utils.py:52-60)
+ * and its gradient in one launch.  pred, target [n_graphs, n] fp32 with n = 36 (a [B, 6, 6]
+ * stiffness) or 21 (the vanilla CGC benchmark's upper triangle).
+ *   out[0] = 100 * mean_b( mean_i (pred - target)^2 / mean_i target^2 )   the loss
+ *   out[1] = mean_b( mean_i (pred - target)^2 )                           logged as 'stiffness_loss'
+ *   grad [n_graphs, n] = grad_scale * d out[0] / d pred   (grad_scale: 1 / accumulate_grad_batches)
+ * One workgroup, one wavefront per graph at a time, every sum in a fixed order that depends on
+ * (n_graphs, n) alone: no atomics, no scratch, bitwise repeatable.  A target row of zeros gives
+ * Inf / NaN as the reference's division does.  -2: n_graphs < 1, n not 36 or 21, a null pointer.
+ *
+ * eelg_sqnorm_parts / eelg_grad_sqnorm: partials[0 .. parts) = sums of squares of contiguous
+ * chunks of grad [numel] (fp32, 16-byte aligned), parts = min(EELG_SQNORM_MAXPARTS,
+ * ceil(numel / EELG_SQNORM_CHUNK)): a function of numel alone, never of the device.  Plain stores,
+ * every partial overwritten on every call, fixed summation order.  A square that overflows fp32
+ * (|g| > 1.8e19) makes the norm Inf.
+ *
+ * eelg_adamw_flat: one launch over flat fp32 buffers of numel elements (16-byte aligned):
+ *   norm  = sqrt(sum of the partials), combined in fp64 in the same order by every block
+ *   coef  = min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_); 1 when max_norm <= 0
+ *   torch.optim.AdamW's rule on (p, m = exp_avg, v = exp_avg_sq, vmax = max_exp_avg_sq; vmax may
+ *   be NULL without amsgrad) with the gradient coef * grad, decoupled decay p *= 1 - lr wd, bias
+ *   corrections from the step count state_in[0] + 1, denom = sqrt(vmax or v) / sqrt(bc2) + eps
+ *   grad  = 0 everywhere
+ * State rows are 4 x int32: {steps taken, launches skipped, bits of the last norm, bits of the
+ * last coefficient}.  The launch reads state_in and writes state_out, which must be two different
+ * rows (the caller alternates them by its own call count), and it does not write the partials:
+ * no block overwrites what another block of the same launch reads.  A norm that is not finite
+ * leaves p, m, v, vmax untouched and the step count as it was, adds one to `skipped`, stores coef
+ * 0, and still zeroes grad.  Hyper-parameters come by value (doubles, as torch holds them).
+ * Vector stores only; no atomics.  -2: numel < 1, a null or misaligned pointer, state_in ==
+ * state_out. */
+#define EELG_SQNORM_CHUNK 8192
+#define EELG_SQNORM_MAXPARTS 1024
+#define EELG_OPTIM_STATE_COLS 4
+int eelg_stiffness_loss(const float* pred, const float* target, int n_graphs, int n, float grad_scale,
+                        float* out, float* grad, void* stream);
+int eelg_sqnorm_parts(long long numel);
+int eelg_grad_sqnorm(const float* grad, long long numel, float* partials, void* stream);
+int eelg_adamw_flat(float* p, float* m, float* v, float* vmax, float* grad, long long numel,
+                    const float* partials, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, double max_norm, int amsgrad, const int* state_in, int* state_out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
