@@ -33,133 +33,131 @@ from gnn import cg, kernel_sets  # noqa: E402
 from gnn.irreps import Ir, Irreps  # noqa: E402
 
 MUL = kernel_sets.MUL
-# receivers per half-wave in tp_fwd (the launcher reads it from the config table)
-TP_NPH = int(os.environ.get("EELG_TP_NPH", "8"))
-# measurement variant (never the product): tp_fwd computes every aggregate but stores none, the
-# lower bound of a forward that hands agg to a fused epilogue instead of HBM
-TP_FWD_NOSTORE = int(os.environ.get("EELG_TP_FWD_NOSTORE", "0"))
-TP_MAXACC = int(os.environ.get("EELG_TP_MAXACC", "64"))
-# the bf16-weight forward's path groups (config 5): smaller groups, 109 instead of 141 VGPRs.
-# r06d / r06e (lmax 3, 5k-node lattices): tp_fwd_tpB_l3_bw 0.477 -> 0.4985 of the roof; at 64
-# for fp32 (config 2: a cap of 40 took tp_fwd from 0.54 to 0.48, r06f)
-TP_MAXACC_BF = int(os.environ.get("EELG_TP_MAXACC_BF", "40"))
-# tp_fwd waves per workgroup (a node tile = 2 x TP_FWD_WPB x TP_NPH receivers; one-wave
-# workgroups refill a freed wave slot at once: r03z kbench 0.505 vs 0.520 ms at 4, 0.518 at 2;
-# in the step 0.438 vs 0.446 ms)
-TP_FWD_WPB = int(os.environ.get("EELG_TP_FWD_WPB", "1"))
-# tp_fwd: the rows of the next two edges (x / SH / weight) prefetched into LDS by LDS-DMA
-# (global_load_lds) instead of a second register set, for fp32 and bf16 weight storage.  One
-# edge in flight by LDS-DMA (r03ag/r03ai: 0.499 vs 0.486 ms kbench) and the register pipeline
-# (0.513 ms; 0.439 vs 0.418 ms in the step) were removed.
-# LDS-DMA tp_fwd: minimum waves per SIMD asked of the register allocator (0: none)
-TP_FWD_WPE = int(os.environ.get("EELG_TP_FWD_WPE", "0"))
-# LDS-DMA tp_fwd: a group's weight slices lead its chunk list, and the LDS-DMA instructions that
-# move only weights carry the nontemporal cache policy (the 705 MB weight stream is read once;
-# the x rows gathered per in-edge stay cacheable).  r04t: in the step 0.418 -> 0.410 ms per launch
-# (roofline 0.535 -> 0.545), kbench 0.500 -> 0.492 ms; the step unchanged
-TP_FWD_WNT = int(os.environ.get("EELG_TP_FWD_WNT", "1"))
-# LDS-DMA tp_fwd: the aggregate rows stored nontemporal (r03l/r03n with the register pipeline:
-# the kernel 3 % faster, the step 0.4 % slower as the following linear missed in L2; r04w: kbench
-# 0.491 -> 0.469 ms, but in the step the kernel itself 0.406 -> 0.418 ms and the step equal)
-TP_FWD_ANT = int(os.environ.get("EELG_TP_FWD_ANT", "0"))
-# LDS-DMA tp_fwd: edges in flight per half-wave (LDS image buffers), fp32 / bf16 weight storage
-TP_FWD_NBUF = int(os.environ.get("EELG_TP_FWD_NBUF", "2"))
-TP_FWD_NBUF_BF = int(os.environ.get("EELG_TP_FWD_NBUF_BF", "2"))
 
-TP_BWD_EPH = int(os.environ.get("EELG_TP_BWD_EPH", "1"))   # edges per half-wave in tp_bwd (4: 0.88 ms, 8: 0.90 ms vs 0.76 ms at 1)
-# tp_bwd: paths whose grad_agg slice + weight are in flight ahead of the path being computed
-# (r03v: 1: 0.781 ms, 2: 0.713, 3: 0.727)
-TP_BWD_PFD = int(os.environ.get("EELG_TP_BWD_PFD", "2"))
-# tp_bwd (fp32): grad_w and gxe stored nontemporal (read back by later kernels: the sender sum,
-# the radial MLP backward on its side stream).  r04r: kbench 0.701 -> 0.683 ms, step +0.3-0.4 %
-TP_BWD_NT = int(os.environ.get("EELG_TP_BWD_NT", "1"))
-# tp_bwd block placement: 0 = 2-D grid (edge block, input-block group), consecutive edge blocks
-# dealt round-robin over the 8 XCDs; 1 = 1-D grid, XCD k takes one contiguous range of edge
-# blocks with the groups of an edge block adjacent; 2 = the same ranges, group-major per XCD.
-# With 0 a receiver whose in-edges straddle two blocks has its grad_agg row fetched into two
-# L2s, and every XCD gathers every lattice's x rows
-TP_BWD_XCD = int(os.environ.get("EELG_TP_BWD_XCD", "2"))
-# tp_bwd: amdgpu_waves_per_eu floor (0: the compiler's 125 VGPRs, 4 waves / SIMD).  Round 6: 5
-# spills 87 VGPRs of tpB_l4 to scratch, 6 spills 303 -- the l4 kernel has no occupancy lever
-TP_BWD_WPE = int(os.environ.get("EELG_TP_BWD_WPE", "0"))
-# fused output-linear grad-x + TP backward (tp_bwf, mul 32; off by default, gnn/ops.py TP_BWF):
-# receivers per workgroup whose [Σ d3 × 32] grad_agg block of one input-block group is computed
-# by MFMA into LDS from the linear's output gradient, then read by the tile's in-edges.
-# r09c kbench (tp_bwd 0.682 + linear grad-x 0.324 ms unfused): R 8 receiver-major 1.417 ms,
-# edge-major 1.242, edge-major without the next-edge prefetch 1.142, the same at R 4 1.104;
-# the MFMA stage alone (R 8) 0.505 ms -- latency-bound at 2 waves / SIMD (LDS and VGPRs)
-TP_BWF_R = int(os.environ.get("EELG_TP_BWF_R", "4"))
-TP_BWF_SKIP = int(os.environ.get("EELG_TP_BWF_SKIP", "0"))   # measurement only: 1 = no edge stage, 2 = no MFMA stage
-TP_BWF_EM = int(os.environ.get("EELG_TP_BWF_EM", "1"))       # edge stage: 1 = the tile's edges dealt over the half-waves
-TP_BWF_NX = int(os.environ.get("EELG_TP_BWF_NX", "0"))       # edge stage: next edge's x / SH / weight loads one edge ahead
-TP_BWF_P1PF = int(os.environ.get("EELG_TP_BWF_P1PF", "1"))   # MFMA stage: next task's operands loaded one task ahead
-# symmetric contraction: coefficient blocks (32 terms each) in flight ahead of the block being
-# computed, and the terms per block, forward / grad-x (r03r/r03s, grad-x: 32 terms 2 ahead
-# 0.407 ms, 64 terms 1 ahead 0.363 ms; 16 terms 3-4 ahead 0.57 ms; the forward: 32 or 40 terms
-# 1 ahead, it spills SGPRs beyond)
-SC_PFD_FWD = int(os.environ.get("EELG_SC_PFD_FWD", "1"))
-SC_BLOCK_FWD = int(os.environ.get("EELG_SC_BLOCK_FWD", "32"))
-SC_PFD_BWD = int(os.environ.get("EELG_SC_PFD_BWD", "1"))
-SC_BLOCK_BWD = int(os.environ.get("EELG_SC_BLOCK_BWD", "64"))
-# fwd / grad-x: 64-node tiles per workgroup; waves w, w + 4, ... run the same channel on
-# consecutive tiles, so their coefficient scalar loads share the CU's scalar cache
-SC_NT = int(os.environ.get("EELG_SC_NT", "1"))
-# fwd / grad-x: a block's coefficients are scalar-loaded as SGPR vectors (16 / 8 / 4 / 2 / 1
-# terms per s_load) and pinned as whole vectors, so the VALU reads them in place; 0 = one float
-# (and one pinned SGPR, hence an s_mov_b32 per term) per coefficient.  r04f kbench: fwd 0.312 vs
-# 0.326 ms, grad-x 0.349 vs 0.357
-SC_CVEC = int(os.environ.get("EELG_SC_CVEC", "1"))
-# fwd / grad-x packed: two nodes per lane (lane, lane + 64 of a 128-node tile) on v_pk_fma_f32,
-# each coefficient broadcast from ONE half of an aligned SGPR pair by op_sel / op_sel_hi (inline
-# asm: the compiler builds (c, c) pairs with an s_mov per odd coefficient instead).  Round-5
-# microbenchmark (tools/proto/valu_ceiling.hip, profiles/r05b_valu.txt): a plain v_fmac_f32 with
-# an SGPR operand issues once per ~4 cycles per SIMD at ANY occupancy (77 TFLOP/s), all-VGPR
-# FMAs reach 118-120 TF and the op_sel-broadcast packed FMA 132-140 TF at 2-4 waves per SIMD
-SC_PK = int(os.environ.get("EELG_SC_PK", "1"))
-# packed grad-x: 32-term blocks (64 with one block ahead spills SGPRs once the volatile packed
-# statements fix the order)
-SC_PK_BLOCK_BWD = int(os.environ.get("EELG_SC_PK_BLOCK_BWD", "32"))
-# packed: 1 = every packed statement a volatile asm in the _PkSched order; 0 = the broadcast FMAs
-# as plain asm and the VGPR products / FMAs as vector C++, in term order, scheduled by the compiler
-SC_PK_SCHED = int(os.environ.get("EELG_SC_PK_SCHED", "1"))
-# packed coefficient operands: "asm" = one aligned SGPR pair per two terms, the odd term broadcast
-# by op_sel in inline asm; "dual" = each block scalar-loaded twice (at t0 and t0 + 1), so every
-# coefficient is the LOW half of an aligned pair, which the compiler broadcasts by itself
-# (op_sel_hi:[0,..]) -- no inline asm, no hazard s_nops, twice the SGPRs per block
-SC_PK_MODE = os.environ.get("EELG_SC_PK_MODE", "asm")
-# coefficient gradient: LDS-resident nodes per workgroup, waves per workgroup, the most
-# accumulators (terms) per wave
-SC_COEF_CHUNK = int(os.environ.get("EELG_SC_COEF_CHUNK", "512"))
-SC_COEF_WAVES = int(os.environ.get("EELG_SC_COEF_WAVES", "16"))
-SC_COEF_MAXJG = int(os.environ.get("EELG_SC_COEF_MAXJG", "64"))
-# coefficient gradient: term groups clustered by shared operands (coef_groups) instead of runs
-# of the term order
-SC_COEF_CLUSTER = int(os.environ.get("EELG_SC_COEF_CLUSTER", "1"))
-# coefficient gradient, streaming form (round 6): a wave owns ONE term group for a whole node
-# range, so its accumulators are zeroed and reduced across the lanes once per range instead of
-# once per 512-node chunk (the round-5 form spent ~21 % of its VALU instructions there); the
-# range's channel-major rows stream through two LDS buffers of SC_COEF_SC nodes filled by
-# LDS-DMA one chunk ahead.  0 = the round-5 chunk-resident kernel
-SC_COEF_STREAM = int(os.environ.get("EELG_SC_COEF_STREAM", "1"))
+# ---------------------------------------------------------------------------
+# build-time knobs
+# ---------------------------------------------------------------------------
+# Tuning parameters of the generated kernels, read from the environment once at import
+# (tools/build_variant.sh builds a second library under other values for an A/B):
+# name -> shipped value.  Every one only sizes or tunes the one emitted form; none selects
+# another kernel.
+KNOBS = {
+    # receivers per half-wave in tp_fwd (the launcher reads it from the config table)
+    "EELG_TP_NPH": 8,
+    # tp_fwd: the most accumulators per lane of a path group, fp32 / bf16 weight storage.  The
+    # bf16-weight forward (config 5) takes smaller groups, 109 instead of 141 VGPRs: r06d / r06e
+    # (lmax 3, 5k-node lattices) tp_fwd_tpB_l3_bw 0.477 -> 0.4985 of the roof; fp32 stays at 64
+    # (config 2: a cap of 40 took tp_fwd from 0.54 to 0.48, r06f)
+    "EELG_TP_MAXACC": 64,
+    "EELG_TP_MAXACC_BF": 40,
+    # tp_fwd waves per workgroup (a node tile = 2 x TP_FWD_WPB x TP_NPH receivers; one-wave
+    # workgroups refill a freed wave slot at once: r03z kbench 0.505 vs 0.520 ms at 4, 0.518 at 2;
+    # in the step 0.438 vs 0.446 ms)
+    "EELG_TP_FWD_WPB": 1,
+    # tp_fwd prefetches the rows of the next edges (x / SH / weight) into LDS by LDS-DMA
+    # (global_load_lds), for fp32 and bf16 weight storage.
+    # minimum waves per SIMD asked of the register allocator (0: none)
+    "EELG_TP_FWD_WPE": 0,
+    # a group's weight slices lead its chunk list, and the LDS-DMA instructions that move only
+    # weights carry the nontemporal cache policy (the 705 MB weight stream is read once; the x
+    # rows gathered per in-edge stay cacheable).  r04t: in the step 0.418 -> 0.410 ms per launch
+    # (roofline 0.535 -> 0.545), kbench 0.500 -> 0.492 ms; the step unchanged
+    "EELG_TP_FWD_WNT": 1,
+    # edges in flight per half-wave (LDS image buffers), fp32 / bf16 weight storage
+    "EELG_TP_FWD_NBUF": 2,
+    "EELG_TP_FWD_NBUF_BF": 2,
+    # tp_bwd: paths whose grad_agg slice + weight are in flight ahead of the path being computed
+    # (r03v: 1: 0.781 ms, 2: 0.713, 3: 0.727)
+    "EELG_TP_BWD_PFD": 2,
+    # tp_bwd (fp32): grad_w and gxe stored nontemporal (read back by later kernels: the sender sum,
+    # the radial MLP backward on its side stream).  r04r: kbench 0.701 -> 0.683 ms, step +0.3-0.4 %
+    "EELG_TP_BWD_NT": 1,
+    # tp_bwd: amdgpu_waves_per_eu floor (0: the compiler's 125 VGPRs, 4 waves / SIMD).  Round 6: 5
+    # spills 87 VGPRs of tpB_l4 to scratch, 6 spills 303 -- the l4 kernel has no occupancy lever
+    "EELG_TP_BWD_WPE": 0,
+    # fused output-linear grad-x + TP backward (tp_bwf, mul 32; off by default, gnn/ops.py TP_BWF):
+    # receivers per workgroup whose [Σ d3 × 32] grad_agg block of one input-block group is computed
+    # by MFMA into LDS from the linear's output gradient, then read by the tile's in-edges.
+    # r09c kbench (tp_bwd 0.682 + linear grad-x 0.324 ms unfused): R 8 receiver-major 1.417 ms,
+    # edge-major 1.242, edge-major without the next-edge prefetch 1.142, the same at R 4 1.104;
+    # the MFMA stage alone (R 8) 0.505 ms -- latency-bound at 2 waves / SIMD (LDS and VGPRs)
+    "EELG_TP_BWF_R": 4,
+    # symmetric contraction: coefficient blocks in flight ahead of the block being computed, and
+    # the terms per block, forward / grad-x (r03r/r03s, grad-x: 32 terms 2 ahead 0.407 ms, 64
+    # terms 1 ahead 0.363 ms; 16 terms 3-4 ahead 0.57 ms; the forward: 32 or 40 terms 1 ahead, it
+    # spills SGPRs beyond).  Grad-x: 32-term blocks (64 with one block ahead spills SGPRs once the
+    # volatile packed statements fix the order)
+    "EELG_SC_PFD_FWD": 1,
+    "EELG_SC_BLOCK_FWD": 32,
+    "EELG_SC_PFD_BWD": 1,
+    "EELG_SC_PK_BLOCK_BWD": 32,
+    # coefficient gradient: LDS-resident nodes per workgroup of the chunk-resident kernel, its
+    # waves per workgroup, the most accumulators (terms) per wave of either kernel
+    "EELG_SC_COEF_CHUNK": 512,
+    "EELG_SC_COEF_WAVES": 16,
+    "EELG_SC_COEF_MAXJG": 64,
+}
+
+# Retired knobs: name -> the shipped value, the only form still generated (what each one selected
+# and what its other values measured: profiles/HISTORY.md).  Setting one to
+# anything else is an error, not a silent default build (check_retired_knobs).
+RETIRED_KNOBS = {
+    "EELG_TP_FWD_NOSTORE": 0,      # measurement variant, never the product
+    "EELG_TP_FWD_ANT": 0,          # nontemporal aggregate stores: kernel slower in the step (r04w)
+    "EELG_TP_BWD_EPH": 1,          # edges per half-wave in tp_bwd: 4 / 8 slower
+    "EELG_TP_BWD_XCD": 2,          # tp_bwd block order: 0 / 1 superseded
+    "EELG_TP_BWF_SKIP": 0,         # measurement only
+    "EELG_TP_BWF_EM": 1,           # tp_bwf edge stage: receiver-major slower (r09c)
+    "EELG_TP_BWF_NX": 0,           # tp_bwf next-edge prefetch: slower (r09c)
+    "EELG_TP_BWF_P1PF": 1,         # tp_bwf MFMA operands one task ahead
+    "EELG_SC_PK": 1,               # unpacked contraction forward / grad-x superseded (round 5)
+    "EELG_SC_NT": 1,               # shaped the unpacked kernels only
+    "EELG_SC_CVEC": 1,             # shaped the unpacked kernels only
+    "EELG_SC_BLOCK_BWD": 64,       # shaped the unpacked kernels only
+    "EELG_SC_PK_MODE": "asm",      # "dual" / "pairs" coefficient loads never shipped
+    "EELG_SC_PK_SCHED": 1,         # compiler-scheduled packed statements
+    "EELG_SC_COEF_CLUSTER": 1,     # term groups as runs of the term order
+    "EELG_SC_COEF_STREAM": 1,      # 0 launched the round-5 chunk-resident kernel alone
+    "EELG_SC_COEF_PAIRS": 0,       # row-pair streamed image: slower (r08f / r08g)
+    "EELG_SC_COEF_PK": 0,          # two nodes per lane in the streamed kernel: slower (r08i)
+    "EELG_SC_COEF_PK_JG": 32,      # its terms per group
+}
+
+
+def _knob(name: str) -> int:
+    return int(os.environ.get(name, KNOBS[name]))
+
+
+def check_retired_knobs(env=None) -> None:
+    """Exit with a message naming the knob if a retired one is set to anything but its shipped
+    value: a variant build would otherwise compile the default under the variant's label."""
+    env = os.environ if env is None else env
+    for name, shipped in RETIRED_KNOBS.items():
+        if name in env and env[name].strip() != str(shipped):
+            sys.exit(f"gen_kernels.py: {name}={env[name]} asks for a variant that is no longer generated "
+                     f"(retired; the shipped value is {shipped}, see profiles/HISTORY.md)")
+
+
+TP_NPH = _knob("EELG_TP_NPH")
+TP_MAXACC = _knob("EELG_TP_MAXACC")
+TP_MAXACC_BF = _knob("EELG_TP_MAXACC_BF")
+TP_FWD_WPB = _knob("EELG_TP_FWD_WPB")
+TP_FWD_WPE = _knob("EELG_TP_FWD_WPE")
+TP_FWD_WNT = _knob("EELG_TP_FWD_WNT")
+TP_FWD_NBUF = _knob("EELG_TP_FWD_NBUF")
+TP_FWD_NBUF_BF = _knob("EELG_TP_FWD_NBUF_BF")
+TP_BWD_PFD = _knob("EELG_TP_BWD_PFD")
+TP_BWD_NT = _knob("EELG_TP_BWD_NT")
+TP_BWD_WPE = _knob("EELG_TP_BWD_WPE")
+TP_BWF_R = _knob("EELG_TP_BWF_R")
+SC_PFD_FWD = _knob("EELG_SC_PFD_FWD")
+SC_BLOCK_FWD = _knob("EELG_SC_BLOCK_FWD")
+SC_PFD_BWD = _knob("EELG_SC_PFD_BWD")
+SC_PK_BLOCK_BWD = _knob("EELG_SC_PK_BLOCK_BWD")
+SC_COEF_CHUNK = _knob("EELG_SC_COEF_CHUNK")
+SC_COEF_WAVES = _knob("EELG_SC_COEF_WAVES")
+SC_COEF_MAXJG = _knob("EELG_SC_COEF_MAXJG")
 SC_COEF_SC = 256                      # nodes per streamed chunk: one 1-KiB LDS-DMA row per wave-instruction
-# streamed image as row pairs read by ds_read_b64 (1), or as rows read by ds_read2st64_b32 (0).
-# Measured (kbench, same boxes): rows 0.402-0.404 ms; pairs 0.578 ms (r08f, the DMA issue loop
-# with per-instruction divisions) and 0.464 ms (r08g, strength-reduced issue: 208 four-byte
-# LDS-DMA instructions per chunk instead of 50 sixteen-byte ones, SALU 55 -> 88 M, issue
-# stalls 186 -> 260 M per launch) -- the halved LDS read cycles do not pay for the fill
-SC_COEF_PAIRS = int(os.environ.get("EELG_SC_COEF_PAIRS", "0"))
-# packed streaming coefficient gradient: two nodes per lane (a ds_read_b64 of two consecutive
-# nodes of a row), v_pk_mul_f32 / v_pk_fma_f32 on node pairs, <= SC_COEF_PK_JG terms per group
-# (two accumulator registers per term).  Measured (r08i, kbench): 0.500-0.506 vs 0.410 ms
-# unpacked -- VALU instructions 208 -> 129 M per launch, but the 32-term groups need 15 sets
-# of workgroups per tile (twice the chunk staging) and a step's compute shrinks 3.5x against a
-# fixed staging and barrier cost (SQ_WAIT_ANY 42 %), so it stays off
-SC_COEF_PK = int(os.environ.get("EELG_SC_COEF_PK", "0"))
-SC_COEF_PK_JG = int(os.environ.get("EELG_SC_COEF_PK_JG", "32"))
-# Variants built, measured slower and removed (DESIGN.md section 3 records the numbers): packed
-# channel-pair TP forward, 2x-unrolled TP edge loop, shared-coupling (M in LDS) and cooperative
-# TP forwards, two nodes / two channels per lane in the contraction, mul-major coefficient
-# gradient operands, two node tiles per contraction workgroup.
 
 fnv1a64 = cg.fnv1a64
 
@@ -659,13 +657,12 @@ def _emit_tp_fwd_glds2(name, groups, din, nshp, dmid, wn, node_off, bf: bool = F
         L.append('      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the image is refilled')
         for h in (0, 1):
             L.append(f"      while (node_{h} < n1_{h} && nend_{h} == e_{h}) {{   // uniform")
-            nost = " && inv_norm < -1.0e30f" if TP_FWD_NOSTORE else ""   # measurement variant only
-            L.append(f"        if (hf == {h}{f' && u < {LW}' if LW < 32 else ''}{nost}) {{")
+            L.append(f"        if (hf == {h}{f' && u < {LW}' if LW < 32 else ''}) {{")
             L.append(f"          float* __restrict__ o = agg + (size_t)node_{h} * {dmid};")
             for p in grp:
                 d3 = 2 * p.l3 + 1
                 L.extend("          " + ln for ln in vec_store([f"a{p.slot}_{k}" for k in range(d3)], "o",
-                                                             f"{p.out_off + cg * LW * d3} + u * {d3}", nt=bool(TP_FWD_ANT)))
+                                                             f"{p.out_off + cg * LW * d3} + u * {d3}"))
             L.append("          " + " ".join(f"{a} = 0.0f;" for a in accs))
             L.append("        }")
             L.append(f"        ++node_{h}; nend_{h} = nend2_{h}; nend2_{h} = rowptr[min(node_{h} + 2, n1_{h})];")
@@ -714,9 +711,9 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
          alpha(l3) Σ_j W_s[u][j] gy[r][off(l3) + j·d3 + m], on v_mfma_f32_32x32x2f32 (rows u,
          columns (r, m), K = j) into LDS -- the [N, dmid] grad_agg tensor of the unfused path
          (written by the linear's grad-x, read back by tp_bwd) never reaches HBM;
-      2. each half-wave streams the in-edges of one receiver (receiver-sorted order: one
-         contiguous range) with tp_bwd's per-path arithmetic, its grad_agg slices read from LDS,
-         storing grad_w and the per-edge grad_x rows (gxe) as tp_bwd does."""
+      2. the tile's in-edges (receiver-sorted order: one contiguous range) are dealt over the 8
+         half-waves, each edge with tp_bwd's per-path arithmetic, its grad_agg slices read from
+         LDS, storing grad_w and the per-edge grad_x rows (gxe) as tp_bwd does."""
     WT = "unsigned short" if bf else "float"
     R = TP_BWF_R
     tab = bwf_slot_table(paths, target)
@@ -747,7 +744,6 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
                  + ", ".join(f"{{{tab[s][0]}, {tab[s][2]}}}" for s in sorted(tab)) + "};")
         L.append(f"static const float bwf_alpha_{name}[{len(paths)}] = {{"
                  + ", ".join(flit(tab[s][1]) for s in sorted(tab)) + "};")
-    EM, NX, P1 = TP_BWF_EM, TP_BWF_NX, TP_BWF_P1PF
     L.append(f"__global__ __launch_bounds__(256) void tp_bwf_{name}{sfx}(")
     L.append(f"    const float* __restrict__ x, const float* __restrict__ sh, const {WT}* __restrict__ w,")
     L.append("    const int* __restrict__ sender, const int* __restrict__ receiver,")
@@ -764,8 +760,8 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
     L.append("  if (n0 >= n_nodes) return;")
     L.append(f"  const int sg = bwf_sg_{name}[by];")
     # ---- stage 1: grad_agg of the group's slots for the tile (MFMA into LDS) ----
-    # the operands of task t + 4 are loaded while task t's MFMAs run (P1)
-    L.append(f"  const int t1 = bwf_tb_{name}[by + 1]{' * 0' if TP_BWF_SKIP == 2 else ''};")
+    # the operands of task t + 4 are loaded while task t's MFMAs run
+    L.append(f"  const int t1 = bwf_tb_{name}[by + 1];")
     L.append("  int t = bwf_tb_" + name + "[by] + wave;")
 
     def p1_load(pre, tv):
@@ -777,14 +773,10 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
                 f"    const eelg_f4a* __restrict__ wp = reinterpret_cast<const eelg_f4a*>(wl + {pre}tk.woff + u * 32 + hf * 16);",
                 f"    {pre}a0 = wp[0]; {pre}a1 = wp[1]; {pre}a2 = wp[2]; {pre}a3 = wp[3];",
                 "    " + " ".join(f"{pre}b[{st}] = {pre}ok ? gp[{st} * {pre}tk.d3] : 0.0f;" for st in range(16)) + " }"]
-    if P1:
-        L.append("  if (t < t1) {")
-        L += ["  " + ln for ln in p1_load("", "t")]
-        L.append("  for (;;) {")
-        L += ["  " + ln for ln in p1_load("n", "t + 4")]
-    else:
-        L.append("  for (; t < t1; t += 4) {")
-        L += p1_load("", "t")
+    L.append("  if (t < t1) {")
+    L += ["  " + ln for ln in p1_load("", "t")]
+    L.append("  for (;;) {")
+    L += ["  " + ln for ln in p1_load("n", "t + 4")]
     L.append("    eelg_f32x16v acc = {};")
     for st in range(16):
         L.append(f"    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a{st // 4}[{st % 4}], b[{st}], acc, 0, 0, 0);")
@@ -793,28 +785,16 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
     L += ["      " + " ".join(f"gd[{(v & 3) + 8 * (v >> 2)} * tk.d3] = acc[{v}] * tk.alpha;" for v in range(v0, v0 + 4))
           for v0 in range(0, 16, 4)]
     L.append("    }")
-    if P1:
-        L.append("    t += 4;")
-        L.append("    if (t >= t1) break;")
-        L.append("    tk = ntk; col = ncol; r = nr; m = nm; ok = nok; a0 = na0; a1 = na1; a2 = na2; a3 = na3;")
-        L.append("    " + " ".join(f"b[{st}] = nb[{st}];" for st in range(16)))
-        L.append("  }}")
-    else:
-        L.append("  }")
+    L.append("    t += 4;")
+    L.append("    if (t >= t1) break;")
+    L.append("    tk = ntk; col = ncol; r = nr; m = nm; ok = nok; a0 = na0; a1 = na1; a2 = na2; a3 = na3;")
+    L.append("    " + " ".join(f"b[{st}] = nb[{st}];" for st in range(16)))
+    L.append("  }}")
     L.append("  __syncthreads();")
     # ---- stage 2: the tile's in-edges, tp_bwd's per-path arithmetic with grad_agg from LDS ----
+    # edge-major: half-wave hw takes edges eb + hw, eb + hw + 8, ... of the tile's range
     L.append("  const int hw = threadIdx.x >> 5;")
-    if TP_BWF_SKIP == 1:
-        L.append("  if (n_nodes > 0) return;")
-    if EM:
-        # edge-major: half-wave hw takes edges eb + hw, eb + hw + 8, ... of the tile's range
-        L.append(f"  const int eb = rowptr[n0] + hw, ee = rowptr[min(n0 + {R}, n_nodes)];")
-        ES = 8
-    else:
-        # receiver-major: half-wave hw streams the in-edges of receiver n0 + hw
-        L.append(f"  if (hw >= {R} || n0 + hw >= n_nodes) return;")
-        L.append("  const int eb = rowptr[n0 + hw], ee = rowptr[n0 + hw + 1];")
-        ES = 1
+    L.append(f"  const int eb = rowptr[n0] + hw, ee = rowptr[min(n0 + {R}, n_nodes)];")
     L.append("  if (eb >= ee) return;")
     L.append("  switch (by) {")
     PF = TP_BWD_PFD
@@ -827,38 +807,22 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
         ys_ = [f"y{l2 * l2 + j}" for l2 in l2s for j in range(2 * l2 + 1)]
         p0 = grp[0]
         L.append(f"  case {gi}: {{ // input block l1 = {l}")
-        if not EM:
-            L.append(f"    const float* __restrict__ gr = Gs + hw * {sg};")
-
-        def edge_loads(pref, sv, ev):
-            out = [f"    {{ const float* __restrict__ xs = x + (size_t){sv} * {din};",
-                   f"      const float* __restrict__ ye = sh + (size_t){ev} * {nshp};",
-                   f"      const {WT}* __restrict__ we = w + (size_t){ev} * {wn} + u;"]
-            out += ["      " + ln for ln in vec_load([pref + v for v in xs_], "xs", f"{node_off[l]} + u * {d}")]
-            out += ["      " + ln for ln in sh_load(l2s, pref, "ye")]
-            out.append(f"      {pref}w{p0.slot} = {ld_w(f'we[{p0.slot * MUL}]')};")
-            out.append("    }")
-            return out
-        carried = xs_ + ys_ + [f"w{p0.slot}"]
-        if NX:
-            L.append("    float " + ", ".join(carried) + ";")
-            L += edge_loads("", "sender[eb]", "eb")
-        L.append(f"    for (int e = eb; e < ee; e += {ES}) {{")
-        if NX:
-            L.append(f"      const bool more = e + {ES} < ee;")
-            L.append(f"      const int sn = more ? sender[e + {ES}] : 0, en = more ? e + {ES} : e;")
-        else:
-            L.append("      float " + ", ".join(carried) + ";")
-            L += ["  " + ln for ln in edge_loads("", "sender[e]", "e")]
-        if EM:
-            L.append(f"      const float* __restrict__ gr = Gs + (receiver[e] - n0) * {sg};")
+        L.append("    for (int e = eb; e < ee; e += 8) {")
+        L.append("      float " + ", ".join(xs_ + ys_ + [f"w{p0.slot}"]) + ";")
+        # the edge's x / SH rows and its first path's weight
+        L.append(f"      {{ const float* __restrict__ xs = x + (size_t)sender[e] * {din};")
+        L.append(f"        const float* __restrict__ ye = sh + (size_t)e * {nshp};")
+        L.append(f"        const {WT}* __restrict__ we = w + (size_t)e * {wn} + u;")
+        L += ["        " + ln for ln in vec_load(xs_, "xs", f"{node_off[l]} + u * {d}")]
+        L += ["        " + ln for ln in sh_load(l2s, "", "ye")]
+        L.append(f"        w{p0.slot} = {ld_w(f'we[{p0.slot * MUL}]')};")
+        L.append("      }")
+        L.append(f"      const float* __restrict__ gr = Gs + (receiver[e] - n0) * {sg};")
         L.append(f"      const {WT}* __restrict__ we = w + (size_t)e * {wn} + u;")
         L.append(f"      {WT}* __restrict__ gwe = gw + (size_t)e * {wn} + u;")
         L.append(f"      {WT}* __restrict__ gxo = gxe + (size_t)e * {din};")
         for i in range(d):
             L.append(f"      float gx{l}_{i} = 0.0f;")
-        if NX:
-            L.append("      float " + ", ".join("n" + v for v in carried) + ";")
         base_pin = xs_ + [f"gx{l}_{i}" for i in range(d)] + ys_
         wregs = {0: [f"w{p0.slot}"]}
         for pj in range(1, min(PF, len(grp))):
@@ -871,13 +835,7 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
                 q = grp[pi + PF]
                 L.append(f"      float w{q.slot} = {ld_w(f'we[{q.slot * MUL}]')};")
                 wregs[pi + PF] = [f"w{q.slot}"]
-            if pi + 1 < len(grp):
-                nxt_regs = wregs[pi + 1]
-            elif NX:                         # next edge's loads in flight during the last path
-                L += ["  " + ln for ln in edge_loads("n", "sn", "en")]
-                nxt_regs = ["n" + v for v in carried]
-            else:
-                nxt_regs = []
+            nxt_regs = wregs[pi + 1] if pi + 1 < len(grp) else []
             L.append(f"      {{ // slot {p.slot}: {p.l1} x {p.l2} -> {p.l3}")
             L.append(f"        const float* __restrict__ gs = gr + {lds_of[p.slot]} + u * {d3};")
             L.append("        const float " + ", ".join(f"g{p.slot}_{k} = gs[{k}]" for k in range(d3)) + ";")
@@ -909,8 +867,6 @@ def _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf,
         else:
             L += ["      " + ln for ln in vec_store([f"gx{l}_{i}" for i in range(d)], "gxo", f"{node_off[l]} + u * {d}",
                                                        nt=bool(TP_BWD_NT))]
-        if NX:
-            L.append("      " + " ".join(f"{v} = n{v};" for v in carried))
         L.append("    }")
         L.append("    break; }")
     L.append("  default: break;")
@@ -983,26 +939,18 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
     L.append("  const int lane = threadIdx.x & 63;")
     # wrow (optional): edge e reads weight row wrow[e] (shared rows); null = row e.  grad_w
     # stays one row per edge, in edge order, either way
-    if TP_BWD_XCD:
-        # 1-D grid of 8 * nb8 * NBG blocks (eelg_capi.hip); block b runs on XCD b % 8, which
-        # takes edge blocks [xcd * nb8, (xcd + 1) * nb8); surplus edge blocks exit below
-        L.append(f"  const int nb8 = gridDim.x / {8 * NBG}, xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;")
-        if TP_BWD_XCD == 1:
-            L.append(f"  const int by = bi % {NBG}, bx = xcd * nb8 + bi / {NBG};")
-        else:
-            L.append(f"  const int by = bi / nb8, bx = xcd * nb8 + bi % nb8;")
-    else:
-        L.append("  const int by = blockIdx.y, bx = blockIdx.x;")
+    # 1-D grid of 8 * nb8 * NBG blocks (eelg_capi.hip); block b runs on XCD b % 8, which takes
+    # edge blocks [xcd * nb8, (xcd + 1) * nb8), group-major (a receiver's grad_agg row and a
+    # lattice's x rows stay in one L2); surplus edge blocks exit below
+    L.append(f"  const int nb8 = gridDim.x / {8 * NBG}, xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;")
+    L.append("  const int by = bi / nb8, bx = xcd * nb8 + bi % nb8;")
     L += [ln.replace("blockIdx.y", "by") for ln in chan_head]
     # spos (optional): gxe row of edge e is spos[e], its position in sender order, so the sender
     # sum reads gxe contiguously instead of gathering rows through sperm
-    # a half-wave streams TP_BWD_EPH consecutive edges: while the last path of edge e
-    # computes, edge e+1's x / SH rows and first path's grad_agg slice and weight are in
-    # flight (its sender / receiver indices were loaded when edge e started)
-    EPH = TP_BWD_EPH
-    L.append(f"  const int e0 = ((bx * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5)) * {EPH};")
+    # a half-wave owns one edge (the emitted loop over [e0, e1) runs once)
+    L.append("  const int e0 = ((bx * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5)) * 1;")
     L.append("  if (e0 >= n_edges) return;")
-    L.append(f"  const int e1 = min(e0 + {EPH}, n_edges);")
+    L.append("  const int e1 = min(e0 + 1, n_edges);")
     L.append(f"  switch ({YSW.replace('blockIdx.y', 'by')}) {{")
     for gi, grp in enumerate(bgroups):
         l = grp[0].l1
@@ -1013,38 +961,25 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
         p0 = grp[0]
         g0_ = [f"g{p0.slot}_{k}" for k in range(2 * p0.l3 + 1)] + [f"w{p0.slot}"]
         L.append(f"  case {gi}: {{ // input block l1 = {l}")
-
-        def edge_loads(pref, sv, rv, ev, qv):
-            """x / SH rows of an edge and its first path's grad_agg slice + weight"""
-            out = [f"    {{ const float* __restrict__ xs = x + (size_t){sv} * {din};",
-                   f"      const float* __restrict__ ye = sh + (size_t){ev} * {nshp};",
-                   f"      const float* __restrict__ ge = gagg + (size_t){rv} * {dmid};",
-                   f"      const {WT}* __restrict__ we = w + (size_t){qv} * {wn} + {UC};"]
-            out += ["      " + ln for ln in vec_load([pref + v for v in xs_], "xs", f"{node_off[l]} + {UC} * {d}")]
-            out += ["      " + ln for ln in sh_load(l2s, pref, "ye")]
-            d3 = 2 * p0.l3 + 1
-            out += ["      " + ln for ln in vec_load([f"{pref}g{p0.slot}_{k}" for k in range(d3)], "ge",
-                                                      f"{p0.out_off} + {UC} * {d3}")]
-            out.append(f"      {pref}w{p0.slot} = {ld_w(f'we[{p0.slot * MUL}]')};")
-            out.append("    }")
-            return out
         L.append("    float " + ", ".join(xs_ + ys_ + g0_) + ";")
         L.append("    int rcur = receiver[e0], qcur = wrow ? wrow[e0] : e0;")
-        L += edge_loads("", "sender[e0]", "rcur", "e0", "qcur")
+        # the edge's x / SH rows and its first path's grad_agg slice + weight
+        L.append(f"    {{ const float* __restrict__ xs = x + (size_t)sender[e0] * {din};")
+        L.append(f"      const float* __restrict__ ye = sh + (size_t)e0 * {nshp};")
+        L.append(f"      const float* __restrict__ ge = gagg + (size_t)rcur * {dmid};")
+        L.append(f"      const {WT}* __restrict__ we = w + (size_t)qcur * {wn} + {UC};")
+        L += ["      " + ln for ln in vec_load(xs_, "xs", f"{node_off[l]} + {UC} * {d}")]
+        L += ["      " + ln for ln in sh_load(l2s, "", "ye")]
+        L += ["      " + ln for ln in vec_load(g0_[:-1], "ge", f"{p0.out_off} + {UC} * {2 * p0.l3 + 1}")]
+        L.append(f"      w{p0.slot} = {ld_w(f'we[{p0.slot * MUL}]')};")
+        L.append("    }")
         L.append("    for (int e = e0; e < e1; ++e) {")
-        if EPH > 1:
-            L.append("      const bool more = e + 1 < e1;")
-            L.append("      const int sn = more ? sender[e + 1] : 0, rn = more ? receiver[e + 1] : 0;")
-            L.append("      const int en = more ? e + 1 : e;")
-            L.append("      const int qn = more ? (wrow ? wrow[e + 1] : e + 1) : qcur;")
         L.append("      const float* __restrict__ ge = gagg + (size_t)rcur * " + str(dmid) + ";")
         L.append(f"      const {WT}* __restrict__ we = w + (size_t)qcur * {wn} + {UC};")
         L.append(f"      {WT}* __restrict__ gwe = gw + (size_t)e * {wn} + {UC};")
         L.append(f"      {WT}* __restrict__ gxo = gxe + (size_t)(spos ? spos[e] : e) * {din};")
         for i in range(d):
             L.append(f"      float gx{l}_{i} = 0.0f;")
-        if EPH > 1:
-            L.append("      float " + ", ".join("n" + v for v in xs_ + ys_ + g0_) + ";")
         base_pin = xs_ + [f"gx{l}_{i}" for i in range(d)] + ys_
 
         def pref(p):
@@ -1066,14 +1001,8 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
             if pi + PF < len(grp):           # path pi + PF's loads in flight during this one
                 code, regs_of[pi + PF] = pref(grp[pi + PF])
                 L += code
-            if pi + 1 < len(grp):
-                # only the next path must have landed after this one; later paths stay in flight
-                nxt_regs = regs_of[pi + 1]
-            elif EPH > 1:                    # next edge's loads in flight during the last path
-                L += ["  " + ln for ln in edge_loads("n", "sn", "rn", "en", "qn")]
-                nxt_regs = ["n" + v for v in xs_ + ys_ + g0_]
-            else:
-                nxt_regs = []
+            # only the next path must have landed after this one; later paths stay in flight
+            nxt_regs = regs_of[pi + 1] if pi + 1 < len(grp) else []
             L.append(f"      {{ // slot {p.slot}: {p.l1} x {p.l2} -> {p.l3}")
             L.append(f"        const float cp = {flit(p.coef)} * inv_norm;")
             nz = _path_cg(p)
@@ -1104,8 +1033,6 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
         else:
             L += ["      " + ln for ln in vec_store([f"gx{l}_{i}" for i in range(d)], "gxo", f"{node_off[l]} + {UC} * {d}",
                                                        nt=bool(TP_BWD_NT))]
-        if EPH > 1:
-            L.append("      " + " ".join(f"{v} = n{v};" for v in xs_ + ys_ + g0_) + " rcur = rn; qcur = qn;")
         L.append("    }")
         L.append("    break; }")
     L.append("  default: break;")
@@ -1204,7 +1131,8 @@ def emit_tp(name: str, node: Irreps, sh: Irreps, target: Irreps, wt: str = "f32"
     if bwf:
         L += _emit_tp_bwf(name, sfx, bgroups, paths, target, din, nshp, wn, node_off, bf, ld_w, st_w)
     info = dict(din=din, dmid=dmid, wn=wn, nsh=nsh, ngroups=len(groups) * CG, nbgroups=len(bgroups) * CG,
-                npaths=len(paths), nph=TP_NPH, beph=TP_BWD_EPH, fwpb=TP_FWD_WPB, bxcd=TP_BWD_XCD,
+                npaths=len(paths), nph=TP_NPH, fwpb=TP_FWD_WPB,
+                beph=1, bxcd=2,     # tp_bwd: one edge per half-wave, the group-major 1-D grid
                 bwf=int(bwf), bwf_r=TP_BWF_R, tdim=target.dim,
                 sig=fnv1a64(tp_signature(node, sh, target)))
     return "\n".join(L), info
@@ -1380,7 +1308,7 @@ def coef_sets(plan, n_sets: int, n_waves: int, jg: int) -> List[List[int]]:
     wave w).  Every chunk ends in a workgroup barrier, so a step lasts as long as the busiest
     SIMD's waves; waves w, w + 4, w + 8, w + 12 share a SIMD (cyclic wave placement), so the
     groups are dealt longest-first to the (set, w mod 4) bin with the least work."""
-    groups = [g for g in coef_groups(plan, 1, jg, n_sets * n_waves, pairs=bool(SC_COEF_PAIRS)) if g]
+    groups = [g for g in coef_groups(plan, 1, jg, n_sets * n_waves) if g]
     assert len(groups) <= n_sets * n_waves, (len(groups), n_sets, n_waves)
     per = n_waves // 4
     bins = {(st, k): [] for st in range(n_sets) for k in range(4)}
@@ -1397,8 +1325,7 @@ def coef_sets(plan, n_sets: int, n_waves: int, jg: int) -> List[List[int]]:
     return out
 
 
-def coef_groups(plan, n_waves: int, jg: int, n_groups: int, lds_w: int = 2,
-                pairs: bool = False) -> List[List[int]]:
+def coef_groups(plan, n_waves: int, jg: int, n_groups: int, lds_w: int = 2) -> List[List[int]]:
     """Term groups of the coefficient gradient, clustered so that a group reads few operands.
 
     A lane (one node) of a group loads every x_a / g_q the group's terms use from LDS once per
@@ -1418,16 +1345,13 @@ def coef_groups(plan, n_waves: int, jg: int, n_groups: int, lds_w: int = 2,
     abcid = np.full(nt, -1, dtype=np.int64)
     ab_ix, abc_ix = {}, {}
     nx = 1 + max(max(a, b, c) for _, (a, b, c), _ in terms)
-    # pairs: an operand costs its LDS row pair (rows 2p, 2p + 1: one ds_read_b64 of the
-    # streaming kernel's image), so the groups gather operands whose partner row is used too
-    f = (lambda i: i // 2) if pairs else (lambda i: i)  # noqa: E731
     for t, (nu, (a, b, c), q) in enumerate(terms):
-        m = (1 << f(a)) | (1 << (nx + f(q)))
+        m = (1 << a) | (1 << (nx + q))
         if nu >= 2:
-            m |= 1 << f(b)
+            m |= 1 << b
             abid[t] = ab_ix.setdefault((a, b), len(ab_ix))
         if nu >= 3:
-            m |= 1 << f(c)
+            m |= 1 << c
             abcid[t] = abc_ix.setdefault((a, b, c), len(abc_ix))
         opm[t] = m
     assert 2 * nx <= 64
@@ -1472,52 +1396,6 @@ def coef_groups(plan, n_waves: int, jg: int, n_groups: int, lds_w: int = 2,
 
 
 def _pk_cload(blk, CE):
-    if SC_PK_MODE == "dual":
-        return _pk_cload_dual(blk, CE)
-    if SC_PK_MODE == "pairs":
-        return _pk_cload_pairs(blk, CE)
-    return _pk_cload_asm(blk, CE)
-
-
-def _pk_cload_pairs(blk, CE):
-    """One 8-byte scalar load per coefficient, at its own offset: the coefficient is the low
-    half of its own aligned SGPR pair (the compiler merges neighbouring loads into wider ones)
-    and only pairs are pinned, never whole vectors"""
-    ts = blk["terms"]
-    out, names = [], []
-    for t in ts:
-        nm = f"cp{t}"
-        out.append(f"  eelg_c2 {nm} = *reinterpret_cast<const eelg_c2*>(cf + {t});")
-        CE[t] = (f"eelg_splat({nm}, 0)", 0)
-        names.append(nm)
-    return out, names
-
-
-def _pk_cload_dual(blk, CE):
-    """Two scalar-load sets of a block's coefficients, at t0 and at t0 + 1 (16 / 8 / 4 / 2 terms
-    per load; rows are padded past the last term): term t0 + i is element i of the first set for
-    even i and element i - 1 of the second for odd i, always an even element, i.e. the low half
-    of an aligned SGPR pair.  CE[t] = the splat expression."""
-    ts = blk["terms"]
-    t0, n = ts[0], len(ts)
-    assert ts == list(range(t0, t0 + n))
-    out, names = [], []
-    for sh, tag in ((0, "a"), (1, "b")):
-        t = t0 + sh
-        cnt = n - sh
-        while cnt > 0:
-            sz = next(z for z in (16, 8, 4, 2) if z <= max(cnt, 2))
-            nm = f"cv{tag}{t}"
-            out.append(f"  eelg_c{sz} {nm} = *reinterpret_cast<const eelg_c{sz}*>(cf + {t});")
-            for i in range(0, min(sz, cnt), 2):
-                CE[t + i] = (f"eelg_splat({nm}, {i})", 0)
-            names.append(nm)
-            t += sz
-            cnt -= sz
-    return out, names
-
-
-def _pk_cload_asm(blk, CE):
     """Scalar loads of a block's coefficients as SGPR vectors of 16 / 8 / 4 / 2 terms (an odd tail
     is loaded as a pair: the row is padded past the last term).  CE[t] = (pair expression, half):
     the aligned SGPR pair holding coefficient t, and which half of it (op_sel)."""
@@ -1558,10 +1436,6 @@ class _PkSched:
 
     def emit(self, ind="  "):
         n = len(self.ins)
-        if not SC_PK_SCHED:
-            out = [ind + t for t, _, _ in self.ins]
-            self.ins = []
-            return out
         deps = [set() for _ in range(n)]
         last_w, reads_since = {}, {}
         for j, (_, w, r) in enumerate(self.ins):
@@ -1608,23 +1482,23 @@ def emit_sc_packed(L, name, plan, lin, lout, D, Dout, TP, NB, NTH, head, stage_i
     every coefficient FMA is one v_pk_fma_f32 whose SGPR operand broadcasts one half of an aligned
     coefficient pair (EELG_PKF_LO / _HI), the pair / triple products and the grad-x chain are
     v_pk_mul_f32 / v_pk_fma_f32 on VGPRs (EELG_PKMV / EELG_PKFV), all scheduled by _PkSched.
-    Same blocks, prefetch and pins as the plain form."""
+    The broadcast is inline asm: the compiler builds (c, c) pairs with an s_mov per odd
+    coefficient instead.  Round-5 microbenchmark (tools/proto/valu_ceiling.hip,
+    profiles/r05b_valu.txt): a plain v_fmac_f32 with an SGPR operand issues once per ~4 cycles
+    per SIMD at ANY occupancy (77 TFLOP/s), all-VGPR FMAs reach 118-120 TF and the
+    op_sel-broadcast packed FMA 132-140 TF at 2-4 waves per SIMD.
+    Each block's coefficients are scalar-loaded SC_PFD_* blocks ahead and pinned at the end of
+    the block before."""
     CE = {}
     S = _PkSched()
 
     def cfma(t, b, c):
         pr, hf = CE[t]
-        if SC_PK_MODE in ("dual", "pairs"):
-            S.add(f"{c} = __builtin_elementwise_fma({pr}, {b}, {c});", [c], [c, b])
-        else:
-            S.add(f"EELG_PKF_{'HI' if hf else 'LO'}({c}, {pr}, {b});", [c], [c, b])
+        S.add(f"EELG_PKF_{'HI' if hf else 'LO'}({c}, {pr}, {b});", [c], [c, b])
 
     def cmul(t, b, c):
         pr, hf = CE[t]
-        if SC_PK_MODE in ("dual", "pairs"):
-            S.add(f"{c} = __builtin_elementwise_fma({pr}, {b}, (eelg_f2r){{0.0f, 0.0f}});", [c], [b])
-        else:
-            S.add(f"EELG_PKM_{'HI' if hf else 'LO'}({c}, {pr}, {b});", [c], [b])
+        S.add(f"EELG_PKM_{'HI' if hf else 'LO'}({c}, {pr}, {b});", [c], [b])
 
     def vmul(d, a, b):
         S.add(f"EELG_PKMV({d}, {a}, {b});", [d], [a, b])
@@ -1717,6 +1591,9 @@ def emit_sc_packed(L, name, plan, lin, lout, D, Dout, TP, NB, NTH, head, stage_i
     L.append("    const float* __restrict__ x, const float* __restrict__ coef,")
     L.append("    const float* __restrict__ gout, int n_nodes, float* __restrict__ gx,")
     L.append("    float* __restrict__ xt, float* __restrict__ gt) {")
+    # one LDS tile, used three times (x in, grad_out in, grad_x out): 2x the occupancy of
+    # separate x / grad_out tiles.  When xt / gt are given, the staged tiles are also written
+    # channel-major (the coefficient gradient's operands) -- no separate transpose pass.
     L.append(f"  __shared__ float tile[{NB} * {TP}];")
     L += head
     L += stage_in("x", "tile", lin, NB, NTH)
@@ -1822,10 +1699,10 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
     """Symmetric contraction kernels.
 
     Layout: x / out rows are e3nn mul-major ([l-block][channel][m]); a workgroup
-    of 4 waves owns 4 consecutive channels ("channel quad") x 64 nodes and stages
+    of 4 waves owns 4 consecutive channels ("channel quad") x 128 nodes and stages
     the quad's 4*D floats per node through LDS with contiguous global segments, so
     every byte of x / out crosses HBM once.  One wave = one channel (wave-uniform,
-    coefficients come through scalar loads), one lane = one node.  The output irreps
+    coefficients come through scalar loads), one lane = two nodes (emit_sc_packed).  The output irreps
     (``ls``, parity (-1)^l) may differ from the coupling irreps of the input (the
     reference's product block maps the interaction irreps onto the hidden irreps)."""
     plan = cg.symcon_plan(coupling, ls, corr)
@@ -1859,7 +1736,7 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
     nt = len(plan.terms)
     # coefficient row stride: 64-B aligned channel rows, at least one float past the last term (the
     # packed kernels load coefficients in pairs)
-    cld = -(-(nt + (1 if SC_PK else 0)) // 16) * 16
+    cld = -(-(nt + 1) // 16) * 16
 
     def lq(lay, a, cl):
         """LDS column of component a for channel-in-quad cl (may be a runtime expr)."""
@@ -1881,49 +1758,8 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
     if lout.comp == lin.comp:
         lout.goff = lin.goff
 
-    NB = 128 if SC_PK else 64 * SC_NT        # nodes per workgroup (fwd / grad-x): one (two packed) per lane
-    NTH = 256 * SC_NT                       # threads per workgroup (fwd / grad-x)
-    VT = "float"
-
-    def vfma(a, b, c):
-        return f"fmaf({a}, {b}, {c})"
-
-    def cfma(t, b, c):
-        """c += coefficient t * b (the coefficient is a wave-uniform SGPR)"""
-        return vfma(CE[t], b, c)
-    CE: Dict[int, str] = {}                 # term -> expression of its (SGPR) coefficient
-
-    def cload(blk):
-        """the scalar loads of block blk's coefficients (a contiguous term range) and the names
-        to pin; records every term's coefficient expression in CE"""
-        ts = blk["terms"]
-        t0, n = ts[0], len(ts)
-        assert ts == list(range(t0, t0 + n))
-        if not SC_CVEC:
-            for t in ts:
-                CE[t] = f"c{t}"
-            return [f"  float c{t} = cf[{t}];" for t in ts], [f"c{t}" for t in ts]
-        out, names, t = [], [], t0
-        while t < t0 + n:
-            sz = next(z for z in (16, 8, 4, 2, 1) if z <= t0 + n - t)
-            nm = f"cv{t}"
-            if sz == 1:
-                out.append(f"  float {nm} = cf[{t}];")
-                CE[t] = nm
-            else:
-                out.append(f"  eelg_c{sz} {nm} = *reinterpret_cast<const eelg_c{sz}*>(cf + {t});")
-                for i in range(sz):
-                    CE[t + i] = f"{nm}[{i}]"
-            names.append(nm)
-            t += sz
-        return out, names
-    zero = "0.0f"
-
-    def lds_get(ptr, col):
-        return f"{ptr}[{col}]"
-
-    def lds_put(ptr, col, v):
-        return f"{ptr}[{col}] = {v};"
+    NB = 128                                # nodes per workgroup (fwd / grad-x): two per lane
+    NTH = 256                               # threads per workgroup (fwd / grad-x)
 
     # Staging between the mul-major rows and the quad tile.  A quad owns, per node and l-block,
     # one run of 4*d floats (d float4, 16-B aligned), so a tile of nb nodes is nb * D float4:
@@ -2015,19 +1851,6 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
         assert tot % 4 == 0 and nb % 4 == 0
         return [ind + ln for ln in out]
 
-    # group terms by (a, b) pair
-    pairs: Dict[Tuple[int, int], Dict] = {}
-    deg1 = []
-    for t, (nu, (a, b, c), q) in enumerate(plan.terms):
-        if nu == 1:
-            deg1.append((t, a, q))
-        else:
-            g = pairs.setdefault((a, b), {"d2": [], "d3": {}})
-            if nu == 2:
-                g["d2"].append((t, q))
-            else:
-                g["d3"].setdefault(c, []).append((t, q))
-
     # block id -> (node tile, channel quad): the MUL / 4 quad workgroups of one node tile run on
     # one XCD (blockIdx % 8), so the lines of the tile's rows that several quads share (a quad
     # owns a 16*d-byte run of each 128*d-byte l-block) are fetched from HBM once, into that
@@ -2038,135 +1861,14 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
                 f"  const int cq = rest_ % {NQ};",
                 f"  const int n0 = ((rest_ / {NQ}) * 8 + xcd) * {nb};",
                 "  if (n0 >= n_nodes) return;   // uniform per workgroup (tile count padded to 8)"]
-    nrow = "lane" if SC_NT == 1 else "((wv >> 2) * 64 + lane)"   # this lane's node row in the tile
     head = tile_map(NB) + [
             "  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;",
             f"  const int c = __builtin_amdgcn_readfirstlane(cq * {Q} + (wv & {Q - 1}));",
             f"  const int cl = __builtin_amdgcn_readfirstlane(wv & {Q - 1});",
             f"  const float* __restrict__ cf = coef + (size_t)c * {cld};"]
 
-    if SC_PK:
-        emit_sc_packed(L, name, plan, lin, lout, D, Dout, TP, NB, NTH, head, stage_in, stage_out,
-                       cm_store, lq)
-    else:
-        # ---------------- forward ----------------
-        L.append(f"__global__ __launch_bounds__({NTH}) void sc_fwd_{name}(")
-        L.append("    const float* __restrict__ x, const float* __restrict__ coef, int n_nodes,")
-        L.append("    float* __restrict__ out) {")
-        L.append(f"  __shared__ float tile[{NB} * {TP}];")
-        L += head
-        L += stage_in("x", "tile", lin, NB, NTH)
-        L.append("  __syncthreads();")
-        L.append(f"  float* __restrict__ tr = tile + {nrow} * {TP};")
-        for a in range(D):
-            L.append(f"  {VT} x{a} = {lds_get('tr', lq(lin, a, 'cl'))};")
-        for q in range(Dout):
-            L.append(f"  {VT} o{q} = {zero};")
-        blocks = sc_blocks(plan, SC_BLOCK_FWD)
-        fv = [f"x{a}" for a in range(D)] + [f"o{q}" for q in range(Dout)]
-        pf = {}
-        for j in range(min(SC_PFD_FWD, len(blocks))):
-            lines, pf[j] = cload(blocks[j])
-            L += lines
-        for bi, blk in enumerate(blocks):
-            # coefficients SC_PFD_FWD blocks ahead are in flight (scalar loads) while this block computes
-            if bi + SC_PFD_FWD < len(blocks):
-                lines, pf[bi + SC_PFD_FWD] = cload(blocks[bi + SC_PFD_FWD])
-                L += lines
-            nxt = [nm for j in range(bi + 1, bi + 1 + SC_PFD_FWD) for nm in pf.get(j, [])]
-            carry = []
-            if blk["kind"] == "deg1":
-                for t, a, q in blk["deg1"]:
-                    L.append(f"  o{q} = {cfma(t, f'x{a}', f'o{q}')};")
-            for sg in blk.get("segs", []):
-                a, b = sg["a"], sg["b"]
-                pv = f"p{a}_{b}"
-                if sg["first"]:
-                    L.append(f"  {VT} {pv} = x{a} * x{b};")
-                for t, q in sg["d2"]:
-                    L.append(f"  o{q} = {cfma(t, pv, f'o{q}')};")
-                for cc, lst in sg["d3"]:
-                    L.append(f"  {{ const {VT} m = {pv} * x{cc};")
-                    for t, q in lst:
-                        L.append(f"    o{q} = {cfma(t, 'm', f'o{q}')};")
-                    L.append("  }")
-                if not sg["last"]:
-                    carry = [pv]
-            L.append("  " + pin(fv + carry, sgprs=nxt))
-        L.append("  __syncthreads();")
-        for q in range(Dout):
-            L.append(f"  {lds_put('tr', lq(lout, q, 'cl'), f'o{q}')}")
-        L.append("  __syncthreads();")
-        L += stage_out("out", "tile", lout, NB, NTH)
-        L.append("}")
-
-
-        # ---------------- backward w.r.t. x ----------------
-        L.append(f"__global__ __launch_bounds__({NTH}) void sc_bwd_x_{name}(")
-        L.append("    const float* __restrict__ x, const float* __restrict__ coef,")
-        L.append("    const float* __restrict__ gout, int n_nodes, float* __restrict__ gx,")
-        L.append("    float* __restrict__ xt, float* __restrict__ gt) {")
-        # one LDS tile, used three times (x in, grad_out in, grad_x out): 2x the occupancy of
-        # separate x / grad_out tiles.  When xt / gt are given, the staged tiles are also written
-        # channel-major (the coefficient gradient's operands) -- no separate transpose pass.
-        L.append(f"  __shared__ float tx[{NB} * {TP}];")
-        L += head
-        L += stage_in("x", "tx", lin, NB, NTH)
-        L.append("  __syncthreads();")
-        L.append("  if (xt) {")
-        L += cm_store("xt", "tx", lin, NB, "    ", NTH)
-        L.append("  }")
-        L.append(f"  float* __restrict__ xr = tx + {nrow} * {TP};")
-        for a in range(D):
-            L.append(f"  {VT} x{a} = {lds_get('xr', lq(lin, a, 'cl'))};")
-            L.append(f"  {VT} d{a} = {zero};")
-        L.append("  __syncthreads();")
-        L += stage_in("gout", "tx", lout, NB, NTH)
-        L.append("  __syncthreads();")
-        L.append("  if (gt) {")
-        L += cm_store("gt", "tx", lout, NB, "    ", NTH)
-        L.append("  }")
-        for q in range(Dout):
-            L.append(f"  {VT} g{q} = {lds_get('xr', lq(lout, q, 'cl'))};")
-        bv = [f"x{a}" for a in range(D)] + [f"g{q}" for q in range(Dout)] + [f"d{a}" for a in range(D)]
-        blocks = sc_blocks(plan, SC_BLOCK_BWD)
-        pf = {}
-        for j in range(min(SC_PFD_BWD, len(blocks))):
-            lines, pf[j] = cload(blocks[j])
-            L += lines
-        for bi, blk in enumerate(blocks):
-            # coefficients SC_PFD_BWD blocks ahead are in flight (scalar loads) while this block computes
-            if bi + SC_PFD_BWD < len(blocks):
-                lines, pf[bi + SC_PFD_BWD] = cload(blocks[bi + SC_PFD_BWD])
-                L += lines
-            nxt = [nm for j in range(bi + 1, bi + 1 + SC_PFD_BWD) for nm in pf.get(j, [])]
-            carry = []
-            if blk["kind"] == "deg1":
-                for t, a, q in blk["deg1"]:
-                    L.append(f"  d{a} = {cfma(t, f'g{q}', f'd{a}')};")
-            for sg in blk.get("segs", []):
-                a, b = sg["a"], sg["b"]
-                pv, sv = f"p{a}_{b}", f"s{a}_{b}"
-                if sg["first"]:
-                    L.append(f"  {VT} {pv} = x{a} * x{b}; {VT} {sv} = {zero};")
-                for t, q in sg["d2"]:
-                    L.append(f"  {sv} = {cfma(t, f'g{q}', sv)};")
-                for cc, lst in sg["d3"]:
-                    L.append(f"  {{ {VT} s = {zero};")
-                    for t, q in lst:
-                        L.append(f"    s = {cfma(t, f'g{q}', 's')};")
-                    L.append(f"    d{cc} = {vfma('s', pv, f'd{cc}')}; {sv} = {vfma('s', f'x{cc}', sv)}; }}")
-                if sg["last"]:
-                    L.append(f"  d{a} = {vfma(sv, f'x{b}', f'd{a}')}; d{b} = {vfma(sv, f'x{a}', f'd{b}')};")
-                else:
-                    carry = [pv, sv]
-            L.append("  " + pin(bv + carry, sgprs=nxt))
-        L.append("  __syncthreads();")
-        for a in range(D):
-            L.append(f"  {lds_put('xr', lq(lin, a, 'cl'), f'd{a}')}")
-        L.append("  __syncthreads();")
-        L += stage_out("gx", "tx", lin, NB, NTH)
-        L.append("}")
+    emit_sc_packed(L, name, plan, lin, lout, D, Dout, TP, NB, NTH, head, stage_in, stage_out,
+                   cm_store, lq)
 
     # ---------------- mul-major -> channel-major transpose ----------------
     # dst[(c * D + a) * n_nodes + n] = src[n, a-th component of channel c]; one kernel per
@@ -2187,22 +1889,37 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
         emit_cmajor(cmajor_out, lout)
 
     # ---------------- backward w.r.t. coefficients ----------------
-    # grad coef[c, t] = sum_n g_q(n) x_a(n) x_b(n) x_c(n).  A workgroup owns one channel and
-    # one chunk of SC_COEF_CHUNK nodes: it stages the chunk's channel-major x / g rows into LDS
-    # ONCE (every byte of xt / gt crosses HBM once per launch), then its SC_COEF_WAVES waves
-    # sweep the staged chunk once per term group (JG accumulators per lane, one lane per node
-    # of a 64-node sub-tile) with no further barrier.  The per-lane sums are reduced over the
-    # 64 lanes by recursive halving (eelg_lane_reduce64), so lane t ends with term t of the
-    # group.  Deterministic partials part[chunk, c, t], summed over chunks by the caller.
+    # the chunk-resident kernel (round 5) and the streaming one (round 6) that the config table
+    # hands the launcher next to it
+    code, njg = emit_sc_coef_chunk(name, plan, D, Dout, cld)
+    L += code
+    code, csets = emit_sc_coef_stream(name, plan, D, Dout, cld)
+    L += code
+    info = dict(D=D, Dout=Dout, drow=drow, orow=orow, nterms=nt, cld=cld, njg=njg, wpb=SC_COEF_WAVES,
+                nbc=SC_COEF_SC, nb=NB, nth=NTH, cmajor_out=cmajor_out, csets=csets, ls=tuple(ls),
+                sig=fnv1a64(sc_signature(coupling, ls, corr)))
+    return "\n".join(L), info
+
+
+def emit_sc_coef_chunk(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[List[str], int]:
+    """Chunk-resident coefficient gradient ``sc_bwd_coef_<name>`` (round 5).
+
+    grad coef[c, t] = sum_n g_q(n) x_a(n) x_b(n) x_c(n).  A workgroup owns one channel and
+    one chunk of SC_COEF_CHUNK nodes: it stages the chunk's channel-major x / g rows into LDS
+    ONCE (every byte of xt / gt crosses HBM once per launch), then its SC_COEF_WAVES waves
+    sweep the staged chunk once per term group (JG accumulators per lane, one lane per node
+    of a 64-node sub-tile) with no further barrier.  The per-lane sums are reduced over the
+    64 lanes by recursive halving (eelg_lane_reduce64), so lane t ends with term t of the
+    group.  Deterministic partials part[chunk, c, t], summed over chunks by the caller.
+    Returns (code, term groups)."""
+    nt = len(plan.terms)
+    L: List[str] = []
     NCB = SC_COEF_CHUNK
     WV = SC_COEF_WAVES
     gpw = -(-nt // (WV * SC_COEF_MAXJG))      # term groups per wave
     JG = -(-nt // (WV * gpw))                 # terms per group (<= 64)
     assert JG <= 64 and NCB % 64 == 0
-    if SC_COEF_CLUSTER:
-        groups = coef_groups(plan, WV, JG, WV * gpw)
-    else:
-        groups = [list(range(s, min(s + JG, nt))) for s in range(0, nt, JG)]
+    groups = coef_groups(plan, WV, JG, WV * gpw)
     # lane j of group g ends with the sum of term perm[g * 64 + j] (-1: no term)
     perm = [(grp[j] if j < len(grp) else -1) for grp in groups for j in range(64)]
     nsub = NCB // 64
@@ -2323,17 +2040,7 @@ def emit_sc(name: str, coupling: str, ls: Tuple[int, ...], corr: int) -> Tuple[s
     L.append("    if (t >= 0) dst[t] = acc[0];")
     L.append("  }")
     L.append("}")
-    WPB, NBC = WV, NCB
-    cstream = 0
-    csets = 0
-    if SC_COEF_STREAM:
-        code, csets = emit_sc_coef_stream(name, plan, D, Dout, cld)
-        L += code
-        cstream, NBC = 1, SC_COEF_SC
-    info = dict(D=D, Dout=Dout, drow=drow, orow=orow, nterms=nt, cld=cld, njg=len(groups), wpb=WPB, nbc=NBC, nb=NB, nth=NTH,
-                cmajor_out=cmajor_out, cstream=cstream, csets=csets, ls=tuple(ls),
-                sig=fnv1a64(sc_signature(coupling, ls, corr)))
-    return "\n".join(L), info
+    return L, len(groups)
 
 
 def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[List[str], int]:
@@ -2352,43 +2059,27 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
     that barrier, its reads retired by their own ``lgkmcnt``.  Operand reads are inline asm (so
     hipcc does not drain the in-flight DMA before them), issued in the order the terms first use
     them, each waited for by a counted ``lgkmcnt`` just before its first use.
-    SC_COEF_PAIRS (round 6): the image is [row pair][node][2] -- rows 2p and 2p + 1 of a node side
-    by side -- so one ``ds_read_b64`` (2 LDS cycles) returns two operands, where the row image
-    needed a ``ds_read2st64_b32`` (4 cycles); the pairs are filled by 4-byte LDS-DMA, 32 nodes x
-    2 rows per wave-instruction (per-lane source offset fixed per workgroup).  An odd row count
-    pads its last pair with a copy of its first row (never read).
     A chunk that passes the range's end, or rows that are not 16-B aligned (N % 4 != 0), are
     staged through registers with zero fill.  Blocks: the S set-blocks of a tile are consecutive
     on one XCD (their rows cross HBM once, then come from that XCD's L2).  part[r, c, t]: one
     deterministic partial per range."""
     WV, SC = 16, SC_COEF_SC
-    PAIRS = SC_COEF_PAIRS
-    PK = SC_COEF_PK and not PAIRS
     nt = len(plan.terms)
-    S = -(-nt // (WV * (SC_COEF_PK_JG if PK else SC_COEF_MAXJG)))
+    S = -(-nt // (WV * SC_COEF_MAXJG))
     JG = -(-nt // (WV * S))
-    assert JG <= (32 if PK else 64)
+    assert JG <= 64
     groups = coef_sets(plan, S, WV, JG)
     ROWS = D + Dout
     NBUF = 3
-    PX, PG = -(-D // 2), -(-Dout // 2)        # row pairs of x and of g (PAIRS)
-    if PAIRS:
-        NP = PX + PG
-        BUFF = NP * SC * 2                     # floats per buffer
-        NINS = NP * (SC // 32)                 # 4-byte DMA instructions per chunk (32 nodes x 2 rows)
-        PB = SC * 8                            # bytes per pair block
-        assert (NP - 1) * PB + (SC // 64 - 1) * 512 <= 65535
-        NW = -(-NINS // WV)
-    else:
-        BUFF = ROWS * SC
-        RB = SC * 4                            # bytes per LDS row (one wave-instruction)
-        assert RB == 1024 and (ROWS - 1) * (RB // 256) + SC // 64 - 1 <= 255
-        NW = -(-ROWS // WV)                    # most DMA rows a wave issues per chunk
+    BUFF = ROWS * SC                           # floats per buffer
+    RB = SC * 4                                # bytes per LDS row (one wave-instruction)
+    assert RB == 1024 and (ROWS - 1) * (RB // 256) + SC // 64 - 1 <= 255
+    NW = -(-ROWS // WV)                        # most DMA rows a wave issues per chunk
     assert NBUF * BUFF * 4 <= 163840
     perm = [(grp[j] if j < len(grp) else -1) for grp in groups for j in range(64)]
     L: List[str] = []
     L.append(f"// streaming coefficient gradient: {S} sets x {WV} term groups of <= {JG} terms, "
-             f"{SC}-node chunks, {'row-pair' if PAIRS else 'row'} image{', two nodes per lane' if PK else ''}")
+             f"{SC}-node chunks, row image")
     L.append(f"__device__ const short sc_coefs_perm_{name}[{len(perm)}] = {{")
     for k in range(0, len(perm), 32):
         L.append("  " + ", ".join(str(v) for v in perm[k: k + 32]) + ",")
@@ -2409,52 +2100,23 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
     L.append(f"  const float* __restrict__ xr = xt + (size_t)c * {D} * n_nodes;")
     L.append(f"  const float* __restrict__ gr = gt + (size_t)c * {Dout} * n_nodes;")
     L.append("  const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) float*)sb_);")
-    if PAIRS:
-        # DMA instruction i = wv + 16 k of a chunk moves pair i / NB32, node block i % NB32; with
-        # NB32 = 8 a wave keeps node block nb = wv & 7 and walks pairs h, h + 2, ... (h = wv >> 3).
-        # Lane l: node 32 nb + l / 2 of row 2p + l % 2 (its element offset lo2, fixed per wave);
-        # the pad row of an odd array repeats row 2p (lo1: in bounds, never read)
-        assert SC // 32 == 8 and WV == 16
-        L.append("  const int h = wv >> 3, nbk = wv & 7;")
-        L.append("  const int lo2 = (lane & 1) * n_nodes + nbk * 32 + (lane >> 1), lo1 = nbk * 32 + (lane >> 1);")
     # stage(b, n0): chunk n0 into buffer b; returns the LDS-DMA instructions this wave issued
     L.append("  auto stage = [&](int b, int n0) -> int {")
     L.append("    if (n0 >= nb1) return 0;")
     L.append(f"    float* __restrict__ dst = sb_ + b * {BUFF};")
     L.append(f"    if (vec && n0 + {SC} <= nb1) {{")
     L.append("      int k = 0;")
-    if PAIRS:
-        # x pairs then g pairs, each a pointer stepping by 2 pairs (4 rows); pads only at the end
-        for (arr, P0, P1, DD, off) in (("xr", 0, PX, D, 0), ("gr", PX, PX + PG, Dout, PX)):
-            L.append(f"      {{ int pp = {P0} + ((h - {P0}) & 1);          // the first pair >= {P0} of this wave's parity")
-            L.append(f"        const float* sp = {arr} + (size_t)(2 * (pp - {off})) * n_nodes + n0;")
-            L.append(f"        for (; pp < {P1}; pp += 2, sp += (size_t)4 * n_nodes, ++k) {{")
-            last_pad = DD % 2 == 1
-            lo = f"(pp == {P1 - 1} ? lo1 : lo2)" if last_pad else "lo2"
-            L.append(f"          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp + {lo}),")
-            L.append(f"              (__attribute__((address_space(3))) void*)(dst + pp * {SC * 2} + nbk * 64), 4, 0, 0);")
-            L.append("        }")
-            L.append("      }")
-    else:
-        L.append(f"      for (int row = wv; row < {ROWS}; row += {WV}, ++k) {{   // wave-uniform")
-        L.append(f"        const float* src = (row < {D} ? xr + (size_t)row * n_nodes : gr + (size_t)(row - {D}) * n_nodes) + n0 + lane * 4;")
-        L.append("        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,")
-        L.append(f"            (__attribute__((address_space(3))) void*)(dst + row * {SC}), 16, 0, 0);")
-    if not PAIRS:
-        L.append("      }")
+    L.append(f"      for (int row = wv; row < {ROWS}; row += {WV}, ++k) {{   // wave-uniform")
+    L.append(f"        const float* src = (row < {D} ? xr + (size_t)row * n_nodes : gr + (size_t)(row - {D}) * n_nodes) + n0 + lane * 4;")
+    L.append("        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,")
+    L.append(f"            (__attribute__((address_space(3))) void*)(dst + row * {SC}), 16, 0, 0);")
+    L.append("      }")
     L.append("      return k;")
     L.append("    } else {")
     L.append(f"      for (int i = threadIdx.x; i < {BUFF}; i += {64 * WV}) {{")
-    if PAIRS:
-        L.append(f"        const int pp = i / {2 * SC}, j = (i - pp * {2 * SC}) >> 1, n = n0 + j;")
-        L.append(f"        const bool isx = pp < {PX};")
-        L.append(f"        const int row = 2 * (isx ? pp : pp - {PX}) + (i & 1);")
-        L.append(f"        const bool ok = n < nb1 && row < (isx ? {D} : {Dout});")
-        L.append("        dst[i] = ok ? (isx ? xr : gr)[(size_t)row * n_nodes + n] : 0.0f;")
-    else:
-        L.append(f"        const int row = i / {SC}, j = i - row * {SC}, n = n0 + j;")
-        L.append(f"        const float* src = row < {D} ? xr + (size_t)row * n_nodes : gr + (size_t)(row - {D}) * n_nodes;")
-        L.append("        dst[i] = n < nb1 ? src[n] : 0.0f;")
+    L.append(f"        const int row = i / {SC}, j = i - row * {SC}, n = n0 + j;")
+    L.append(f"        const float* src = row < {D} ? xr + (size_t)row * n_nodes : gr + (size_t)(row - {D}) * n_nodes;")
+    L.append("        dst[i] = n < nb1 ? src[n] : 0.0f;")
     L.append("      }")
     L.append('      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // stores done before the barrier')
     L.append("      return 0;")
@@ -2466,28 +2128,21 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
         L.append(f'    {"if" if k == NW else "else if"} (p >= {k}) asm volatile("s_waitcnt vmcnt({k})" ::: "memory");')
     L.append('    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");')
     L.append("  };")
-    if PK:
-        L.append(f"  eelg_f2r acc[{JG}];")
-        L.append("#pragma unroll")
-        L.append(f"  for (int i = 0; i < {JG}; ++i) acc[i] = (eelg_f2r){{0.0f, 0.0f}};")
-    else:
-        L.append("  float acc[64];")
-        L.append("#pragma unroll")
-        L.append("  for (int i = 0; i < 64; ++i) acc[i] = 0.0f;")
+    L.append("  float acc[64];")
+    L.append("#pragma unroll")
+    L.append("  for (int i = 0; i < 64; ++i) acc[i] = 0.0f;")
     L.append("  stage(0, nb0);")
     L.append(f"  int pend = stage(1, nb0 + {SC});           // this wave's DMAs of the chunk after the current")
     # the chunk loop sits inside each case: the accumulators never meet at a merge point inside
     # the loop (a switch inside the loop made the compiler move all 64 of them at every case exit
     # and spill); every wave, a group-less one too, runs the same stages and barriers
-    lane_b = 8 if (PAIRS or PK) else 4       # bytes per lane of a sub-tile row read
-    NST = 128 if PK else 64                  # nodes per sub-tile
     head = ["      int b = 0;",
             f"      for (int n0 = nb0; n0 < nb1; n0 += {SC}, b = b == {NBUF - 1} ? 0 : b + 1) {{",
             "        retire(pend);                         // chunk n0 landed (this wave's part)",
             '        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");',
             "        __builtin_amdgcn_s_barrier();        // every wave's part; the buffer restaged next is free",
             f"        pend = stage(b == 0 ? 2 : b - 1, n0 + {2 * SC});",
-            f"        const unsigned ab = lds0 + b * {BUFF * 4} + lane * {lane_b};"]
+            f"        const unsigned ab = lds0 + b * {BUFF * 4} + lane * 4;"]
     tail = ["      }",
             '      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");']
     L.append("  switch (jg) {")
@@ -2498,8 +2153,9 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
         L += head
         cpin = pin([f"acc[{jj}]" for jj in range(len(grp))])
         L.append("#pragma unroll 1")
-        L.append(f"      for (int sb = 0; sb < {SC // NST}; ++sb) {{")
-        L.append(f"        const unsigned a_ = ab + sb * {64 * lane_b};")
+        # 64-node sub-tiles, one node (4 bytes of every row) per lane
+        L.append(f"      for (int sb = 0; sb < {SC // 64}; ++sb) {{")
+        L.append("        const unsigned a_ = ab + sb * 256;")
         order = sorted(range(len(grp)), key=lambda jj: (plan.terms[grp[jj]][0] > 1,) + plan.terms[grp[jj]][1])
         seq = []
         for jj in order:
@@ -2508,35 +2164,13 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
                       [("x", a), ("x", b_)] + ([("x", cc)] if nu == 3 else []) + [("g", qq)]):
                 if o not in seq:
                     seq.append(o)
-        if PAIRS:
-            # a read = one row pair: (kind, pair) in first-use order; it yields both rows
-            def pair_of(o):
-                return (o[0], o[1] // 2)
-            reads = []
-            for o in seq:
-                if pair_of(o) not in reads:
-                    reads.append(pair_of(o))
-            ridx = {o: reads.index(pair_of(o)) for o in seq}
-            used = set(seq)
-        elif PK:
-            reads = [(o,) for o in seq]           # one row per read, two nodes
-            ridx = {o: k for k, rd in enumerate(reads) for o in rd}
-        else:
-            reads = [tuple(seq[k: k + 2]) for k in range(0, len(seq), 2)]
-            ridx = {o: k for k, rd in enumerate(reads) for o in rd}
+        # a read = two rows (one ds_read2st64_b32), in first-use order
+        reads = [tuple(seq[k: k + 2]) for k in range(0, len(seq), 2)]
+        ridx = {o: k for k, rd in enumerate(reads) for o in rd}
         row = {o: (o[1] if o[0] == "x" else D + o[1]) for o in seq}
-        VT = "eelg_f2r" if PK else "float"
-        L.append(f"        {VT} " + ", ".join(f"{o[0]}{o[1]}" for o in seq) + ";")
+        L.append("        float " + ", ".join(f"{o[0]}{o[1]}" for o in seq) + ";")
         for k, rd in enumerate(reads):
-            if PAIRS:
-                kind, pp = rd
-                blk = pp if kind == "x" else PX + pp
-                L.append(f"        eelg_f2r p{k};")
-                L.append(f'        asm volatile("ds_read_b64 %0, %1 offset:{blk * PB}" : "=v"(p{k}) : "v"(a_));')
-            elif PK:
-                L.append(f"        eelg_f2r p{k};")
-                L.append(f'        asm volatile("ds_read_b64 %0, %1 offset:{row[rd[0]] * RB}" : "=v"(p{k}) : "v"(a_));')
-            elif len(rd) == 2:
+            if len(rd) == 2:
                 L.append(f"        eelg_f2r p{k};")
                 L.append(f'        asm volatile("ds_read2st64_b32 %0, %1 offset0:{row[rd[0]] * (RB // 256)} '
                          f'offset1:{row[rd[1]] * (RB // 256)}" : "=v"(p{k}) : "v"(a_));')
@@ -2555,13 +2189,7 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
                      ", ".join(f'"+v"({v})' for v in regs) + ' : : "memory");')
             for j in range(state["w"] + 1, k + 1):
                 rd = reads[j]
-                if PAIRS:
-                    kind, pp = rd
-                    parts = [f"{kind}{2 * pp + h} = p{j}[{h}];" for h in (0, 1) if (kind, 2 * pp + h) in used]
-                    L.append("        " + " ".join(parts))
-                elif PK:
-                    L.append(f"        {rd[0][0]}{rd[0][1]} = p{j};")
-                elif len(rd) == 2:
+                if len(rd) == 2:
                     L.append(f"        {rd[0][0]}{rd[0][1]} = p{j}[0]; {rd[1][0]}{rd[1][1]} = p{j}[1];")
                 else:
                     L.append(f"        {rd[0][0]}{rd[0][1]} = p{j};")
@@ -2570,29 +2198,27 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
         for jj in order:
             t = grp[jj]
             nu, (a, b_, cc), qq = plan.terms[t]
-            FMA = (lambda u, v, w: f"__builtin_elementwise_fma({u}, {v}, {w})") if PK else \
-                (lambda u, v, w: f"fmaf({u}, {v}, {w})")
             if nu == 1:
                 need(("x", a), ("g", qq))
-                L.append(f"        acc[{jj}] = {FMA(f'x{a}', f'g{qq}', f'acc[{jj}]')};")
+                L.append(f"        acc[{jj}] = fmaf(x{a}, g{qq}, acc[{jj}]);")
                 continue
             if cur != (a, b_):
                 if cur is not None:
                     L.append("        }")
                     L.append("        " + cpin)
                 need(("x", a), ("x", b_))
-                L.append(f"        {{ const {VT} pp = x{a} * x{b_};")
+                L.append(f"        {{ const float pp = x{a} * x{b_};")
                 cur, curc = (a, b_), None
             if nu == 2:
                 need(("g", qq))
-                L.append(f"          acc[{jj}] = {FMA('pp', f'g{qq}', f'acc[{jj}]')};")
+                L.append(f"          acc[{jj}] = fmaf(pp, g{qq}, acc[{jj}]);")
             else:
                 if curc != cc:
                     need(("x", cc))
-                    L.append(f"          const {VT} m{cc} = pp * x{cc};")
+                    L.append(f"          const float m{cc} = pp * x{cc};")
                     curc = cc
                 need(("g", qq))
-                L.append(f"          acc[{jj}] = {FMA(f'm{cc}', f'g{qq}', f'acc[{jj}]')};")
+                L.append(f"          acc[{jj}] = fmaf(m{cc}, g{qq}, acc[{jj}]);")
         if cur is not None:
             L.append("        }")
         L.append("        " + cpin)
@@ -2603,18 +2229,9 @@ def emit_sc_coef_stream(name: str, plan, D: int, Dout: int, cld: int) -> Tuple[L
     L += [ln for ln in head if "const unsigned ab" not in ln] + tail
     L.append("      break; }")
     L.append("  }")
-    if PK:
-        # the two nodes of each lane first, then the 64 lanes
-        L.append("  float red[64];")
-        L.append("#pragma unroll")
-        L.append(f"  for (int i = 0; i < 64; ++i) red[i] = i < {JG} ? acc[i < {JG} ? i : 0][0] + acc[i < {JG} ? i : 0][1] : 0.0f;")
-        L.append("  eelg_lane_reduce64(red);")
-        L.append(f"  const int t = sc_coefs_perm_{name}[jg * 64 + lane];")
-        L.append(f"  if (t >= 0) part[((size_t)r * {MUL} + c) * {cld} + t] = red[0];")
-    else:
-        L.append("  eelg_lane_reduce64(acc);")
-        L.append(f"  const int t = sc_coefs_perm_{name}[jg * 64 + lane];")
-        L.append(f"  if (t >= 0) part[((size_t)r * {MUL} + c) * {cld} + t] = acc[0];")
+    L.append("  eelg_lane_reduce64(acc);")
+    L.append(f"  const int t = sc_coefs_perm_{name}[jg * 64 + lane];")
+    L.append(f"  if (t >= 0) part[((size_t)r * {MUL} + c) * {cld} + t] = acc[0];")
     L.append("}")
     return L, S
 
@@ -2629,7 +2246,7 @@ def _sc_table_row(name: str, i: dict, outputs: bool = False) -> str:
     return (f'  {{"{name}", {i["D"]}, {i["Dout"]}, {i["drow"]}, {i["orow"]}, {i["nterms"]}, {i["njg"]}, {i["wpb"]}, '
             f'0x{i["sig"]:016x}ULL, sc_fwd_{name}, sc_bwd_x_{name}, sc_bwd_coef_{name}, sc_cmajor_{name}, '
             f'{i["cmajor_out"]}, {i["nbc"]}, {i["nb"]}, {i["nth"]}, {i["cld"]}, '
-            f'{"sc_bwd_coefs_" + name if i["cstream"] else "nullptr"}, {i["csets"]}{tail}}},')
+            f'sc_bwd_coefs_{name}, {i["csets"]}{tail}}},')
 
 
 def _tp_table_row(name: str, i: dict, bf: bool) -> str:
@@ -2661,9 +2278,8 @@ def _write_if_changed(path: str, src: str) -> None:
 
 
 def main(outdir: str) -> None:
+    check_retired_knobs()
     os.makedirs(outdir, exist_ok=True)
-    global _PKV
-    _PKV = "volatile" if SC_PK_SCHED else ""
     parts = ["// GENERATED by csrc/gen_kernels.py -- do not edit", "#include <hip/hip_runtime.h>",
              "#include <stdint.h>", '#include "../eelg_internal.h"', "",
              "// dword-aligned vector types: per-lane runs of d floats start at 4-byte boundaries",
@@ -2680,16 +2296,15 @@ def main(outdir: str) -> None:
              "typedef float eelg_f2r __attribute__((ext_vector_type(2)));",
              "// packed contraction: acc (two nodes) += / = coefficient x b, the coefficient broadcast from",
              "// the low / high half of an aligned SGPR pair by op_sel / op_sel_hi",
-             f'#define EELG_PKF_LO(acc, cp, b) asm {_PKV}("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(cp), "v"(b))',
-             f'#define EELG_PKF_HI(acc, cp, b) asm {_PKV}("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "s"(cp), "v"(b))',
+             '#define EELG_PKF_LO(acc, cp, b) asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(cp), "v"(b))',
+             '#define EELG_PKF_HI(acc, cp, b) asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "s"(cp), "v"(b))',
              # the first term of a sum: an FMA onto the inline constant 0, not a v_pk_mul with op_sel
              # (a VOP3P multiply with a broadcast operand costs its reader an s_nop)
-             f'#define EELG_PKM_LO(acc, cp, b) asm {_PKV}("v_pk_fma_f32 %0, %1, %2, 0 op_sel_hi:[0,1,1]" : "=v"(acc) : "s"(cp), "v"(b))',
-             f'#define EELG_PKM_HI(acc, cp, b) asm {_PKV}("v_pk_fma_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(acc) : "s"(cp), "v"(b))',
-             ('#define EELG_PKMV(d, a, b) asm volatile("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b))'
-              if SC_PK_SCHED else '#define EELG_PKMV(d, a, b) ((d) = (a) * (b))'),
-             ('#define EELG_PKFV(d, a, b) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b))'
-              if SC_PK_SCHED else '#define EELG_PKFV(d, a, b) ((d) = __builtin_elementwise_fma((a), (b), (d)))'),
+             '#define EELG_PKM_LO(acc, cp, b) asm volatile("v_pk_fma_f32 %0, %1, %2, 0 op_sel_hi:[0,1,1]" : "=v"(acc) : "s"(cp), "v"(b))',
+             '#define EELG_PKM_HI(acc, cp, b) asm volatile("v_pk_fma_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(acc) : "s"(cp), "v"(b))',
+             '#define EELG_PKMV(d, a, b) asm volatile("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b))',
+             '#define EELG_PKFV(d, a, b) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b))',
+             # (eelg_splat: no kernel uses it any more; dropping it would change the generated text)
              "template <typename V> __device__ __forceinline__ eelg_f2r eelg_splat(V v, int i) {",
              "  return (eelg_f2r){v[i], v[i]};",
              "}",

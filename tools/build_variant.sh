@@ -1,6 +1,8 @@
 #!/bin/bash
 # Build a kernel variant of libeelg.so into variants/libeelg_<tag>.so with generator env overrides
-# (EELG_* knobs of csrc/gen_kernels.py) and optional EXTRA hipcc flags, through the same Makefile.
+# (the EELG_* knobs of the KNOBS table in csrc/gen_kernels.py; a retired knob, RETIRED_KNOBS there,
+# set to anything but its shipped value fails the build) and optional EXTRA hipcc flags, through
+# the same Makefile.
 # usage: EELG_TP_MAXACC=48 tools/build_variant.sh <tag>     (load it with EELG_LIB=...)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
