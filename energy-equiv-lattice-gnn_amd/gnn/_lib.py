@@ -242,11 +242,7 @@ def tp_config(name: str) -> Tuple[int, Dict[str, int], int]:
     idx = lib.eelg_tp_find(name.encode())
     if idx < 0:
         check(idx, f"tp config {name}")
-    info = (ctypes.c_int * 7)()
-    sig = ctypes.c_uint64()
-    check(lib.eelg_tp_info(idx, ctypes.cast(info, _P), ctypes.cast(ctypes.byref(sig), _P)), "tp_info")
-    keys = ("din", "dmid", "wn", "nsh", "ngroups", "npaths", "lmax")
-    return idx, dict(zip(keys, list(info))), sig.value
+    return (idx,) + _tp_info(idx)
 
 
 def sc_config(name: str) -> Tuple[int, Dict[str, int], int]:

@@ -68,11 +68,8 @@ class _CGCConv(torch.autograd.Function):
         pr = dense.linear_fwd(x, w, 2 * d, d, w_off=d, ld=3 * d, bias=b)
         ep = dense.linear_fwd(edge_ft, w, 2 * d, d, w_off=2 * d, ld=3 * d)
         agg = torch.empty(n, d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("cgc_fwd")
-        _lib.check(_lib.load().eelg_cgc_fwd(
-            _lib.ptr(ps), _lib.ptr(pr), _lib.ptr(ep), _lib.ptr(csr.sender), _lib.ptr(csr.rowptr),
-            _lib.ptr(row_scale), n, d, _lib.ptr(agg), _lib.stream(agg)), "cgc_fwd")
-        ops.TIMER.stop(tok)
+        ops._launch("cgc_fwd", _lib.load().eelg_cgc_fwd, ps, pr, ep, csr.sender, csr.rowptr,
+                    row_scale, n, d, agg, on=agg, timed="cgc_fwd")
         ctx.save_for_backward(x, edge_ft, ps, pr, ep, w, row_scale)
         ctx.csr = csr
         return agg
@@ -85,11 +82,8 @@ class _CGCConv(torch.autograd.Function):
         g = ops._f32(g).contiguous()
         dz = torch.empty(csr.num_edges, 2 * d, device=x.device, dtype=torch.float32)
         gr = torch.empty(n, 2 * d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("cgc_bwd")
-        _lib.check(_lib.load().eelg_cgc_bwd(
-            _lib.ptr(ps), _lib.ptr(pr), _lib.ptr(ep), _lib.ptr(csr.sender), _lib.ptr(csr.rowptr),
-            _lib.ptr(row_scale), n, d, _lib.ptr(g), _lib.ptr(dz), _lib.ptr(gr), _lib.stream(g)), "cgc_bwd")
-        ops.TIMER.stop(tok)
+        ops._launch("cgc_bwd", _lib.load().eelg_cgc_bwd, ps, pr, ep, csr.sender, csr.rowptr,
+                    row_scale, n, d, g, dz, gr, on=g, timed="cgc_bwd")
         gs = ops.segment_sum_csr(dz, csr.srowptr, n, idx=csr.sperm)   # per-sender sums of dz
         dws, dwr, db = _cgc_dw(x, gs, gr, True)
         dwe = dense.linear_bwd_w(edge_ft, dz)
@@ -122,18 +116,12 @@ class _CGCConvEF(torch.autograd.Function):
         ps = dense.linear_fwd(x, w, 2 * d, d, w_off=0, ld=3 * d)
         pr = dense.linear_fwd(x, w, 2 * d, d, w_off=d, ld=3 * d, bias=b)
         agg = torch.empty(n, d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("cgc_fwd_res" if residual else "cgc_fwd")
         if residual:
-            _lib.check(_lib.load().eelg_cgc_fwd_ef_res(
-                _lib.ptr(ps), _lib.ptr(pr), _lib.ptr(ef), _lib.ptr(ea), _lib.ptr(csr.sender),
-                _lib.ptr(csr.rowptr), _lib.ptr(row_scale), n, d, _lib.ptr(x), _lib.ptr(agg),
-                _lib.stream(agg)), "cgc_fwd_ef_res")
+            ops._launch("cgc_fwd_ef_res", _lib.load().eelg_cgc_fwd_ef_res, ps, pr, ef, ea, csr.sender,
+                        csr.rowptr, row_scale, n, d, x, agg, on=agg, timed="cgc_fwd_res")
         else:
-            _lib.check(_lib.load().eelg_cgc_fwd_ef(
-                _lib.ptr(ps), _lib.ptr(pr), _lib.ptr(ef), _lib.ptr(ea), _lib.ptr(csr.sender),
-                _lib.ptr(csr.receiver), _lib.ptr(csr.rowptr), _lib.ptr(row_scale), n, d, _lib.ptr(agg),
-                _lib.stream(agg)), "cgc_fwd_ef")
-        ops.TIMER.stop(tok)
+            ops._launch("cgc_fwd_ef", _lib.load().eelg_cgc_fwd_ef, ps, pr, ef, ea, csr.sender,
+                        csr.receiver, csr.rowptr, row_scale, n, d, agg, on=agg, timed="cgc_fwd")
         ctx.save_for_backward(x, ea, ef, ps, pr, w, row_scale)
         ctx.csr, ctx.residual = csr, residual
         return agg
@@ -149,12 +137,8 @@ class _CGCConvEF(torch.autograd.Function):
         lib = _lib.load()
         nparts = int(lib.eelg_cgc_bwd_ef_parts(n))
         dea_part = torch.empty(nparts, 6, 2 * d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("cgc_bwd")
-        _lib.check(lib.eelg_cgc_bwd_ef(
-            _lib.ptr(ps), _lib.ptr(pr), _lib.ptr(ef), _lib.ptr(ea), _lib.ptr(csr.sender),
-            _lib.ptr(csr.receiver), _lib.ptr(csr.rowptr), _lib.ptr(row_scale), n, d, _lib.ptr(g),
-            _lib.ptr(dz), _lib.ptr(gr), _lib.ptr(dea_part), _lib.stream(g)), "cgc_bwd_ef")
-        ops.TIMER.stop(tok)
+        ops._launch("cgc_bwd_ef", lib.eelg_cgc_bwd_ef, ps, pr, ef, ea, csr.sender, csr.receiver,
+                    csr.rowptr, row_scale, n, d, g, dz, gr, dea_part, on=g, timed="cgc_bwd")
         gs = ops.segment_sum_csr(dz, csr.srowptr, n, idx=csr.sperm)
         dws, dwr, db = _cgc_dw(x, gs, gr, True)
         # d ea = ef^T dz: the kernel's per-workgroup partials (rows 0..5), summed in a fixed order

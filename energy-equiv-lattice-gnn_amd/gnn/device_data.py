@@ -15,7 +15,6 @@ model of the package (``batch.csr`` is the dict ``EnergyEquivGNN.edge_graph`` ac
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
@@ -256,7 +255,7 @@ class DeviceLoader:
         """The collated batch of the graphs ``graph_ids`` (host integers; repeats allowed), each
         rotated by its ``Q`` (``[B, 3, 3]``, or one ``[3, 3]`` for all; host or device, any float
         dtype, used in fp32) or left as stored when ``Q`` is ``None``."""
-        from .ops import TIMER
+        from .ops import _launch
         dds = self.dds
         dev = dds.device
         if dev.type != "cuda":
@@ -338,17 +337,11 @@ class DeviceLoader:
             setattr(out, k, b.csr[k].data_ptr() or None)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            stream = _lib.stream(b.positions)
-            tok = TIMER.start("batch_assemble")
-            _lib.check(lib.eelg_batch_assemble(ctypes.byref(self._source()), _lib.ptr(sdev), _lib.ptr(q_dev),
-                                               nb, n_nodes, n_edges, ctypes.byref(out), stream),
-                       "batch_assemble")
-            TIMER.stop(tok)
+            _launch("batch_assemble", lib.eelg_batch_assemble, self._source(), sdev, q_dev, nb, n_nodes,
+                    n_edges, out, on=b.positions, timed="batch_assemble")
             sel = sdev[4 * ld:o_rel]
             for key in ("stiffness", "compliance"):
                 if key in t:
-                    tok = TIMER.start("mandel_rotate")
-                    _lib.check(lib.eelg_mandel_rotate(_lib.ptr(t[key]), len(dds), _lib.ptr(sel), _lib.ptr(q_dev),
-                                                      nb, _lib.ptr(getattr(b, key)), stream), "mandel_rotate")
-                    TIMER.stop(tok)
+                    _launch("mandel_rotate", lib.eelg_mandel_rotate, t[key], len(dds), sel, q_dev, nb,
+                            getattr(b, key), on=b.positions, timed="mandel_rotate")
         return b

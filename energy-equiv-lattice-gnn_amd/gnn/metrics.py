@@ -104,18 +104,15 @@ def stiffness_metrics(pred: torch.Tensor, target: torch.Tensor, directions: torc
             return rows
         out.copy_(rows)
         return out
-    from .ops import TIMER
+    from .ops import _launch
     pred = pred.to(torch.float32).contiguous()
     target = target.to(torch.float32).contiguous()
     directions = directions.to(torch.float32).contiguous()
     if out is None:
         out = torch.empty((nb, len(METRIC_COLUMNS)), dtype=torch.float32, device=target.device)
     with torch.cuda.device(target.device):
-        tok = TIMER.start("stiffness_metrics")
-        _lib.check(_lib.load().eelg_stiffness_metrics(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(directions),
-                                                      nb, int(directions.shape[0]), float(scale), _lib.ptr(out),
-                                                      _lib.stream(target)), "stiffness_metrics")
-        TIMER.stop(tok)
+        _launch("stiffness_metrics", _lib.load().eelg_stiffness_metrics, pred, target, directions, nb,
+                int(directions.shape[0]), float(scale), out, on=target, timed="stiffness_metrics")
     return out
 
 

@@ -40,11 +40,8 @@ class _NNConvFn(torch.autograd.Function):
             raise ValueError(f"NNConv shapes: x {tuple(x.shape)}, h {tuple(h.shape)}, w3 {tuple(w3.shape)}, "
                              f"b3 {tuple(b3.shape)}, csr {csr.num_nodes} nodes / {e} edges")
         msg = torch.empty(e, d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("nnconv_fwd")
-        _lib.check(_lib.load().eelg_nnconv_fwd(
-            _lib.ptr(x), _lib.ptr(h), _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(csr.sender), e, d,
-            _lib.ptr(msg), _lib.stream(msg)), "nnconv_fwd")
-        ops.TIMER.stop(tok)
+        ops._launch("nnconv_fwd", _lib.load().eelg_nnconv_fwd, x, h, w3, b3, csr.sender, e, d, msg,
+                    on=msg, timed="nnconv_fwd")
         ctx.save_for_backward(x, h, w3, b3)
         ctx.csr = csr
         return ops.segment_sum_csr(msg, csr.rowptr, n)
@@ -59,12 +56,8 @@ class _NNConvFn(torch.autograd.Function):
         lib = _lib.load()
         gxe = torch.empty(e, d, device=x.device, dtype=torch.float32)
         gh = torch.empty(e, d, device=x.device, dtype=torch.float32)
-        tok = ops.TIMER.start("nnconv_bwd_edge")
-        _lib.check(lib.eelg_nnconv_bwd_edge(
-            _lib.ptr(x), _lib.ptr(h), _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(csr.sender),
-            _lib.ptr(csr.receiver), e, d, _lib.ptr(g), _lib.ptr(gxe), _lib.ptr(gh), _lib.stream(g)),
-            "nnconv_bwd_edge")
-        ops.TIMER.stop(tok)
+        ops._launch("nnconv_bwd_edge", lib.eelg_nnconv_bwd_edge, x, h, w3, b3, csr.sender,
+                    csr.receiver, e, d, g, gxe, gh, on=g, timed="nnconv_bwd_edge")
         gx = ops.segment_sum_csr(gxe, csr.srowptr, n, idx=csr.sperm)   # per-sender sums
         gw3 = gb3 = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
@@ -75,12 +68,8 @@ class _NNConvFn(torch.autograd.Function):
                 tot = torch.zeros(d * d * (d + 1), device=x.device, dtype=torch.float32)
             else:
                 part = torch.empty(nparts, d * d * (d + 1), device=x.device, dtype=torch.float32)
-                tok = ops.TIMER.start("nnconv_bwd_w")
-                _lib.check(lib.eelg_nnconv_bwd_w(
-                    _lib.ptr(x), _lib.ptr(h), _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(csr.sender),
-                    _lib.ptr(csr.receiver), e, d, _lib.ptr(g), _lib.ptr(part), _lib.stream(g)),
-                    "nnconv_bwd_w")
-                ops.TIMER.stop(tok)
+                ops._launch("nnconv_bwd_w", lib.eelg_nnconv_bwd_w, x, h, w3, b3, csr.sender,
+                            csr.receiver, e, d, g, part, on=g, timed="nnconv_bwd_w")
                 tot = ops.sum_rows(part)          # the edge splits' partials, fixed order
             gw3, gb3 = tot[:d * d * d].view(d * d, d), tot[d * d * d:]
         return gx, gh, gw3, gb3, None

@@ -5,6 +5,7 @@ There is no eager/CPU fallback: a missing library or a CPU tensor raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -51,6 +52,18 @@ class KernelTimer:
 
 TIMER = KernelTimer()
 
+
+def _launch(name: str, fn, *args, on: torch.Tensor, timed: Optional[str] = None) -> None:
+    """``fn(*args, stream)`` on the current stream of ``on``'s device, checked under the error
+    label ``name``; ``timed``: the ``TIMER`` label of the launch.  Tensors and None pass as
+    addresses, ctypes structures by reference, numbers and raw addresses as they are; dtype,
+    layout and alignment are the caller's."""
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor)
+            else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args]
+    tok = TIMER.start(timed) if timed is not None else None
+    _lib.check(fn(*argv, _lib.stream(on)), name)
+    TIMER.stop(tok)
+
 # side-stream overlap of independent work (radial MLPs, symmetric-contraction coefficient
 # chain and its gradient); EELG_OVERLAP=0 runs everything in line on the current stream
 OVERLAP = os.environ.get("EELG_OVERLAP", "1") != "0"
@@ -71,13 +84,13 @@ RADIAL_CHAIN = os.environ.get("EELG_RADIAL_CHAIN", "1") != "0"
 # grad_x in fp32 instead of from per-edge terms rounded to bf16; with round 3-6's edge kernel
 # (deeper prefetch, XCD-ordered blocks) the edge path is faster (r08m, two alternating pairs:
 # 1145.6 / 1143.7 vs 1130.0 / 1127.9 graphs/s; tp_bwd 1.90 vs tp_bws 2.23 ms per launch)
+_TBS = os.environ.get("EELG_TP_BWD_SENDER", "0")
+TP_BWD_SENDER = None if _TBS == "auto" else _TBS != "0"
 # edge-order backward: gxe rows stored at their sender-order position (eelg_tp_bwd_sorted), so
 # the sender sum reads them contiguously instead of gathering through sperm.  Bitwise-equal
 # results; measured equal (r02s3: sender sum 169 -> 137 us, tp_bwd 1036 -> 1128 us from the
 # scattered row stores; 1844 / 1855 vs 1844 / 1847 graphs/s), so off by default.
 TP_BWD_SPOS = os.environ.get("EELG_TP_BWD_SPOS", "0") != "0"
-_TBS = os.environ.get("EELG_TP_BWD_SENDER", "0")
-TP_BWD_SENDER = None if _TBS == "auto" else _TBS != "0"
 # fused backward of the interaction's output linear and the TP (eelg_tp_bwd_fused): the
 # linear's grad-x [N, dmid] is computed per receiver tile into LDS inside the TP backward instead
 # of being written to HBM by the linear and read back by tp_bwd.  Measured slower (r09c kbench:
@@ -306,13 +319,10 @@ class _EdgeEmbed(torch.autograd.Function):
         gsh, gfeats = _strided_rows(gsh), _f32(gfeats)
         gvec = torch.empty(e, 4, device=pos.device, dtype=torch.float32)
         grad = torch.empty(e, device=pos.device, dtype=torch.float32)
-        tok = TIMER.start("edge_embed_bwd")
-        _lib.check(_lib.load().eelg_edge_embed_bwd(
-            _lib.ptr(pos), _lib.ptr(csr.sender), _lib.ptr(csr.receiver), _lib.ptr(shifts),
-            _lib.ptr(radius), e, lmax, nb, len_end, rad_end, _lib.ptr(gsh), int(gsh.stride(0)) if e else
-            (lmax + 1) ** 2, _lib.ptr(gfeats), _lib.ptr(gvec), _lib.ptr(grad), _lib.stream(gvec)),
-            "edge_embed_bwd")
-        TIMER.stop(tok)
+        _launch("edge_embed_bwd", _lib.load().eelg_edge_embed_bwd, pos, csr.sender, csr.receiver,
+                shifts, radius, e, lmax, nb, len_end, rad_end, gsh,
+                int(gsh.stride(0)) if e else (lmax + 1) ** 2, gfeats, gvec, grad, on=gvec,
+                timed="edge_embed_bwd")
         gpos = None
         if ctx.needs_input_grad[0]:
             n = csr.num_nodes
@@ -404,11 +414,8 @@ def segment_sum_long(src: torch.Tensor, rowptr: torch.Tensor, n_rows: int,
     n_split = max(1, min(64, -(-2048 // max(n_rows, 1))))
     work = torch.empty(n_rows, n_split, width, device=src.device, dtype=torch.float32)
     out = torch.empty(n_rows, width, device=src.device, dtype=torch.float32)
-    tok = TIMER.start("segment_sum_split")
-    _lib.check(_lib.load().eelg_segment_sum_split(
-        _lib.ptr(src), _lib.ptr(rowptr), None, _lib.ptr(row_scale), float(scale), n_rows, width,
-        n_split, _lib.ptr(work), _lib.ptr(out), _lib.stream(out)), "segment_sum_split")
-    TIMER.stop(tok)
+    _launch("segment_sum_split", _lib.load().eelg_segment_sum_split, src, rowptr, None, row_scale,
+            float(scale), n_rows, width, n_split, work, out, on=out, timed="segment_sum_split")
     return out
 
 
@@ -546,11 +553,8 @@ class _SegmentPNA(torch.autograd.Function):
         amax = torch.empty_like(amin)
         # no edges: the kernel reads no row of src, but takes no null pointer
         s = src if src.numel() else torch.zeros(4, device=dev, dtype=torch.float32)
-        tok = TIMER.start("segment_pna_fwd")
-        _lib.check(_lib.load().eelg_segment_pna_fwd(
-            _lib.ptr(s), _lib.ptr(rowptr), _lib.ptr(coef), n_rows, width, _lib.ptr(out), _lib.ptr(mean),
-            _lib.ptr(std), _lib.ptr(amin), _lib.ptr(amax), _lib.stream(out)), "segment_pna_fwd")
-        TIMER.stop(tok)
+        _launch("segment_pna_fwd", _lib.load().eelg_segment_pna_fwd, s, rowptr, coef, n_rows, width,
+                out, mean, std, amin, amax, on=out, timed="segment_pna_fwd")
         if args is not None:
             args.argmin, args.argmax = amin, amax
         ctx.save_for_backward(src, rowptr, scalers, coef, mean, std, amin, amax)
@@ -568,12 +572,8 @@ class _SegmentPNA(torch.autograd.Function):
         part = torch.empty(parts, n_rows * 4, device=src.device, dtype=torch.float32)
         s = src if src.numel() else torch.zeros(4, device=src.device, dtype=torch.float32)
         o = gs if gs.numel() else torch.empty(4, device=src.device, dtype=torch.float32)
-        tok = TIMER.start("segment_pna_bwd")
-        _lib.check(lib.eelg_segment_pna_bwd(
-            _lib.ptr(s), _lib.ptr(rowptr), _lib.ptr(coef), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(amin),
-            _lib.ptr(amax), _lib.ptr(g), n_rows, width, _lib.ptr(o), _lib.ptr(part), _lib.stream(part)),
-            "segment_pna_bwd")
-        TIMER.stop(tok)
+        _launch("segment_pna_bwd", lib.eelg_segment_pna_bwd, s, rowptr, coef, mean, std, amin, amax,
+                g, n_rows, width, o, part, on=part, timed="segment_pna_bwd")
         gw = None
         if ctx.needs_input_grad[1]:
             gcoef = (part[0] if parts == 1 else sum_rows(part)).view(n_rows, 4)
@@ -671,52 +671,79 @@ class _TPInteraction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, sh, w = ctx.saved_tensors
-        csr, info = ctx.csr, ctx.info
-        g = _f32(g)
-        e = csr.num_edges
-        gw = torch.empty_like(w)                       # same storage type as w
-        lib = _lib.load()
-        # the SH gradient (geometry gradients only): its own kernel, one padded row per edge
-        gsh = _tp_bwd_sh(ctx, x, w, g) if ctx.needs_input_grad[1] else None
-        sender = TP_BWD_SENDER if TP_BWD_SENDER is not None else w.dtype == torch.bfloat16
-        if sender:
-            # sender-order pass: grad_x summed per sender in registers, no gxe round trip
-            gx = torch.empty(csr.num_nodes, info["din"], device=x.device, dtype=torch.float32)
-            bws = lib.eelg_tp_bwd_sender_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_sender
-            tok = TIMER.start(f"tp_bwd_sender[din={info['din']}]")
-            _lib.check(bws(ctx.cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(csr.sperm),
-                           _lib.ptr(csr.srowptr), _lib.ptr(csr.receiver), csr.num_nodes,
-                           _lib.ptr(g), float(ctx.inv_norm), _lib.ptr(gw), _lib.ptr(gx),
-                           _lib.stream(gx)), "tp_bwd_sender")
-            TIMER.stop(tok)
-            return gx, gsh, gw, None, None, None, None
-        gxe = torch.empty(e, info["din"], device=x.device, dtype=w.dtype)
-        spos = csr.sender_pos() if TP_BWD_SPOS else None
-        bwd = lib.eelg_tp_bwd_sorted_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_sorted
-        tok = TIMER.start(f"tp_bwd[din={info['din']}]")
-        _lib.check(bwd(ctx.cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(csr.sender),
-                       _lib.ptr(csr.receiver), _lib.ptr(spos), e, _lib.ptr(g), float(ctx.inv_norm),
-                       _lib.ptr(gw), _lib.ptr(gxe), _lib.stream(gxe)), "tp_bwd")
-        TIMER.stop(tok)
-        gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes,
-                             idx=None if spos is not None else csr.sperm)
-        return gx, gsh, gw, None, None, None, None
+        return _tp_bwd(x, sh, w, ctx.csr, ctx.cfg, ctx.info, ctx.inv_norm, g,
+                       want_sh=ctx.needs_input_grad[1]) + (None,) * 4
 
 
-def _tp_bwd_sh(ctx, x, w, g):
+def _tp_bwd(x, sh, w, csr: EdgeCSR, cfg: int, info, inv_norm: float, g, want_sh: bool = False):
+    """(grad_x, grad_sh or None, grad_w) of the interaction over per-edge weights, from the
+    operands as ``_tp_fwd`` returned them: in sender order (``TP_BWD_SENDER``) or in edge order"""
+    g = _f32(g)
+    gw = torch.empty_like(w)                       # same storage type as w
+    # the SH gradient (geometry gradients only): its own kernel, one padded row per edge
+    gsh = _tp_bwd_sh(x, w, csr, cfg, info, inv_norm, g) if want_sh else None
+    if TP_BWD_SENDER if TP_BWD_SENDER is not None else w.dtype == torch.bfloat16:
+        return _tp_bwd_sender(x, sh, w, csr, cfg, info, inv_norm, g, gw), gsh, gw
+    return _tp_bwd_edges(x, sh, w, csr, cfg, info, inv_norm, g, gw), gsh, gw
+
+
+def _tp_bwd_sender(x, sh, w, csr: EdgeCSR, cfg: int, info, inv_norm: float, g, gw):
+    """the sender-order launch: grad_x summed per sender in registers, no gxe round trip"""
+    gx = torch.empty(csr.num_nodes, info["din"], device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    bws = lib.eelg_tp_bwd_sender_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_sender
+    _launch("tp_bwd_sender", bws, cfg, x, sh, w, csr.sperm, csr.srowptr, csr.receiver,
+            csr.num_nodes, g, float(inv_norm), gw, gx, on=gx, timed=f"tp_bwd_sender[din={info['din']}]")
+    return gx
+
+
+def _tp_bwd_launch(x, sh, w, csr: EdgeCSR, cfg: int, info, inv_norm: float, g, gw, gxe,
+                   row=None, spos=None, chunk=None) -> None:
+    """THE edge-order backward launch (``eelg_tp_bwd_rows[_bf16]``): per-edge ``gw`` and ``gxe``
+    ([E, wn] / [E, din], of ``w``'s dtype) from ``g`` [N, dmid].  ``row``: the weight row of each
+    edge (``StrutMap.row``; None: ``w`` is per edge).  ``spos``: where each edge's ``gxe`` row
+    goes (``EdgeCSR.sender_pos``; None: in place).  ``chunk`` = (n0, e0, e1): only the edges
+    e0:e1, whose receivers start at node n0, ``g`` holding the rows from n0 on; the receiver
+    indices are global, so ``g``'s address is offset back by n0 rows."""
+    lib = _lib.load()
+    bwd = lib.eelg_tp_bwd_rows_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_rows
+    e, per_edge = csr.num_edges, (sh, w, row, csr.sender, csr.receiver, g, gw, gxe)
+    if chunk is not None:
+        n0, e0, e1 = chunk
+        e, esz = e1 - e0, w.element_size()
+        off = (4 * e0 * sh.stride(0), esz * e0 * info["wn"], 4 * e0, 4 * e0, 4 * e0,
+               -4 * n0 * info["dmid"], esz * e0 * info["wn"], esz * e0 * info["din"])
+        per_edge = [None if t is None else t.data_ptr() + o for t, o in zip(per_edge, off)]
+    sh, w, row, sender, receiver, g, gw, gxa = per_edge
+    _launch("tp_bwd", bwd, cfg, x, sh, w, row, sender, receiver, spos, e, g, float(inv_norm), gw,
+            gxa, on=gxe, timed=f"tp_bwd[din={info['din']}]")
+
+
+def _tp_sender_sum(gxe, csr: EdgeCSR, spos=None):
+    """grad_x [N, din] fp32: the sender segment sum of the per-edge ``gxe`` rows, which lie in
+    sender order when the launch stored them through ``spos``, else gathered through ``sperm``"""
+    return segment_sum_csr(gxe, csr.srowptr, csr.num_nodes, idx=None if spos is not None else csr.sperm)
+
+
+def _tp_bwd_edges(x, sh, w, csr: EdgeCSR, cfg: int, info, inv_norm: float, g, gw, row=None):
+    """grad_x of the edge-order backward (launch + sender sum, ``TP_BWD_SPOS`` read here); the
+    per-edge weight gradient goes to ``gw``"""
+    gxe = torch.empty(csr.num_edges, info["din"], device=x.device, dtype=w.dtype)
+    spos = csr.sender_pos() if TP_BWD_SPOS else None
+    _tp_bwd_launch(x, sh, w, csr, cfg, info, inv_norm, g, gw, gxe, row=row, spos=spos)
+    return _tp_sender_sum(gxe, csr, spos)
+
+
+def _tp_bwd_sh(x, w, csr: EdgeCSR, cfg: int, info, inv_norm: float, g):
     """``eelg_tp_bwd_sh``: grad of the interaction w.r.t. its SH operand, [E, nsh] (a view of the
     padded rows the kernel writes, pad = 0)"""
-    csr, info = ctx.csr, ctx.info
     if w.dtype != torch.float32:
         raise NotImplementedError("the SH gradient of the interaction takes fp32 TP weights; "
                                   "bf16 storage (storage_dtype='bfloat16') has no geometry gradients")
     e, nsh = csr.num_edges, info["nsh"]
     gsh = torch.empty(e, sh_row_stride(nsh), device=x.device, dtype=torch.float32)
-    tok = TIMER.start(f"tp_bwd_sh[din={info['din']}]")
-    _lib.check(_lib.load().eelg_tp_bwd_sh(
-        ctx.cfg, _lib.ptr(x), None, _lib.ptr(w), _lib.ptr(csr.sender), _lib.ptr(csr.receiver), e,
-        _lib.ptr(g), float(ctx.inv_norm), _lib.ptr(gsh), _lib.stream(gsh)), "tp_bwd_sh")
-    TIMER.stop(tok)
+    _launch("tp_bwd_sh", _lib.load().eelg_tp_bwd_sh, cfg, x, None, w, csr.sender, csr.receiver, e,
+            g, float(inv_norm), gsh, on=gsh, timed=f"tp_bwd_sh[din={info['din']}]")
     return gsh[:, :nsh]
 
 
@@ -770,23 +797,11 @@ class _TPInteractionRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, sh, w = ctx.saved_tensors
-        csr, info, smap = ctx.csr, ctx.info, ctx.smap
-        g = _f32(g)
-        e = csr.num_edges
-        gw = torch.empty(e, info["wn"], device=x.device, dtype=w.dtype)    # per edge, as ever
-        gxe = torch.empty(e, info["din"], device=x.device, dtype=w.dtype)
-        spos = csr.sender_pos() if TP_BWD_SPOS else None
-        lib = _lib.load()
-        bwd = lib.eelg_tp_bwd_rows_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_rows
-        tok = TIMER.start(f"tp_bwd[din={info['din']}]")
-        _lib.check(bwd(ctx.cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(smap.row),
-                       _lib.ptr(csr.sender), _lib.ptr(csr.receiver), _lib.ptr(spos), e, _lib.ptr(g),
-                       float(ctx.inv_norm), _lib.ptr(gw), _lib.ptr(gxe), _lib.stream(gxe)), "tp_bwd")
-        TIMER.stop(tok)
+        csr, info = ctx.csr, ctx.info
+        gw = torch.empty(csr.num_edges, info["wn"], device=x.device, dtype=w.dtype)  # per edge, as ever
+        gx = _tp_bwd_edges(x, sh, w, csr, ctx.cfg, info, ctx.inv_norm, _f32(g), gw, row=ctx.smap.row)
         if ctx.needs_input_grad[2]:                 # else nobody will take it: keep nothing alive
             ctx.box.gw = gw
-        gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes,
-                             idx=None if spos is not None else csr.sperm)
         return gx, None, (_zero1(x.device) if ctx.needs_input_grad[2] else None), None, None, None, None, None
 
 
@@ -854,13 +869,9 @@ def _tp_fwd(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int], inv_norm: fl
     n_out = csr.rowptr.shape[0] - 1
     agg = torch.empty(n_out, info["dmid"], device=x.device, dtype=torch.float32)
     lib = _lib.load()
-    tok = TIMER.start(f"tp_fwd[din={info['din']}]")
     fwd = lib.eelg_tp_fwd_rows_bf16 if bf else lib.eelg_tp_fwd_rows
-    _lib.check(fwd(cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w),
-                   _lib.ptr(smap.row) if smap is not None else None, _lib.ptr(csr.sender),
-                   _lib.ptr(csr.rowptr), n_out, float(inv_norm), _lib.ptr(agg), _lib.stream(agg)),
-               "tp_fwd")
-    TIMER.stop(tok)
+    _launch("tp_fwd", fwd, cfg, x, sh, w, smap.row if smap is not None else None, csr.sender,
+            csr.rowptr, n_out, float(inv_norm), agg, on=agg, timed=f"tp_fwd[din={info['din']}]")
     return agg, x, sh, w
 
 
@@ -951,14 +962,10 @@ class _TPInteractionLinear(torch.autograd.Function):
         gxe = torch.empty(csr.num_edges, info["din"], device=x.device, dtype=w.dtype)
         lib = _lib.load()
         bwf = lib.eelg_tp_bwd_fused_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_fused
-        tok = TIMER.start(f"tp_bwf[din={info['din']}]")
-        _lib.check(bwf(ctx.cfg, _lib.ptr(x), _lib.ptr(sh), _lib.ptr(w), _lib.ptr(csr.sender),
-                       _lib.ptr(csr.receiver), _lib.ptr(csr.rowptr), csr.num_nodes, _lib.ptr(gy), _lib.ptr(lwc),
-                       float(ctx.inv_norm), _lib.ptr(gw), _lib.ptr(gxe), _lib.stream(gxe)),
-                   "tp_bwd_fused")
-        TIMER.stop(tok)
-        gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes, idx=csr.sperm)
-        return gx, None, gw, gW, gb, None, None, None, None, None, None, None
+        _launch("tp_bwd_fused", bwf, ctx.cfg, x, sh, w, csr.sender, csr.receiver, csr.rowptr,
+                csr.num_nodes, gy, lwc, float(ctx.inv_norm), gw, gxe, on=gxe,
+                timed=f"tp_bwf[din={info['din']}]")
+        return _tp_sender_sum(gxe, csr), None, gw, gW, gb, None, None, None, None, None, None, None
 
 
 def _chunk_bounds(csr: EdgeCSR, chunks: int):
@@ -986,25 +993,12 @@ def _tp_linear_bwd_chunked(ctx, x, sh, w, lw, gy, gw):
     consumed while it is still in the MALL; tp_bwd's receiver indices are global, so its grad_agg
     pointer is offset back by the chunk's first row"""
     csr, info, lin = ctx.csr, ctx.info, ctx.lin
-    lib = _lib.load()
-    dmid, din, wn = info["dmid"], info["din"], info["wn"]
-    gxe = torch.empty(csr.num_edges, din, device=x.device, dtype=w.dtype)
-    esz = w.element_size()
-    bwd = lib.eelg_tp_bwd_sorted_bf16 if w.dtype == torch.bfloat16 else lib.eelg_tp_bwd_sorted
+    gxe = torch.empty(csr.num_edges, info["din"], device=x.device, dtype=w.dtype)
     for n0, n1, e0, e1 in _chunk_bounds(csr, ctx.chunks):
         gagg = lin._bwd_x(gy[n0:n1], lw)
-        if e1 <= e0:
-            continue
-        tok = TIMER.start(f"tp_bwd[din={din}]")
-        _lib.check(bwd(ctx.cfg, _lib.ptr(x), sh.data_ptr() + 4 * e0 * sh.stride(0),
-                       w.data_ptr() + esz * e0 * wn, csr.sender.data_ptr() + 4 * e0,
-                       csr.receiver.data_ptr() + 4 * e0, None, e1 - e0,
-                       gagg.data_ptr() - 4 * n0 * dmid, float(ctx.inv_norm),
-                       gw.data_ptr() + esz * e0 * wn, gxe.data_ptr() + esz * e0 * din,
-                       _lib.stream(gxe)), "tp_bwd")
-        TIMER.stop(tok)
-    gx = segment_sum_csr(gxe, csr.srowptr, csr.num_nodes, idx=csr.sperm)
-    return gx, None, gw
+        if e1 > e0:
+            _tp_bwd_launch(x, sh, w, csr, ctx.cfg, info, ctx.inv_norm, gagg, gw, gxe, chunk=(n0, e0, e1))
+    return _tp_sender_sum(gxe, csr), None, gw
 
 
 def tp_interaction_linear(x, sh, w, csr: EdgeCSR, cfg: int, info: Dict[str, int],
@@ -1063,11 +1057,8 @@ class _SymCon(torch.autograd.Function):
         if x.shape[1] != mul * info["D"] or coef.shape != (mul, info["coef_ld"]):
             raise ValueError(f"shape mismatch: x {tuple(x.shape)} coef {tuple(coef.shape)} vs mul {mul}, {info}")
         out = torch.empty(n, mul * info["Dout"], device=x.device, dtype=torch.float32)
-        lib = _lib.load()
-        tok = TIMER.start("sc_fwd")
-        _lib.check(lib.eelg_sc_fwd_rows(cfg, _lib.ptr(x), x.shape[1], _lib.ptr(coef), n, mul,
-                                        _lib.ptr(out), out.shape[1], _lib.stream(out)), "sc_fwd")
-        TIMER.stop(tok)
+        _launch("sc_fwd", _lib.load().eelg_sc_fwd_rows, cfg, x, x.shape[1], coef, n, mul, out,
+                out.shape[1], on=out, timed="sc_fwd")
         ctx.save_for_backward(x, coef)
         ctx.cfg, ctx.info, ctx.mul, ctx.side = cfg, info, mul, side
         return out
@@ -1097,28 +1088,16 @@ class _SymCon(torch.autograd.Function):
             for t in (x, g, xt, gt):
                 t.record_stream(side)
             with torch.cuda.stream(side):
-                _lib.check(lib.eelg_sc_cmajor(ctx.cfg, 0, _lib.ptr(x), n, ctx.mul, _lib.ptr(xt),
-                                              _lib.stream(xt)), "sc_cmajor")
-                _lib.check(lib.eelg_sc_cmajor(ctx.cfg, 1, _lib.ptr(g), n, ctx.mul, _lib.ptr(gt),
-                                              _lib.stream(gt)), "sc_cmajor")
+                _sc_cmajor_pair(ctx.cfg, x, g, n, ctx.mul, xt, gt)
         if want_x:
             gx = torch.empty_like(x)
-            tok = TIMER.start("sc_bwd_x")
             fuse = want_c and not cm_side
-            _lib.check(lib.eelg_sc_bwd_x_rows(ctx.cfg, _lib.ptr(x), x.shape[1], _lib.ptr(coef),
-                                              _lib.ptr(g), g.shape[1], n, ctx.mul, _lib.ptr(gx),
-                                              _lib.ptr(xt) if fuse else None,
-                                              _lib.ptr(gt) if fuse else None, _lib.stream(gx)),
-                       "sc_bwd_x")
-            TIMER.stop(tok)
+            _launch("sc_bwd_x", lib.eelg_sc_bwd_x_rows, ctx.cfg, x, x.shape[1], coef, g, g.shape[1],
+                    n, ctx.mul, gx, xt if fuse else None, gt if fuse else None, on=gx,
+                    timed="sc_bwd_x")
         if want_c:
             if not (want_x or cm_side):
-                tok = TIMER.start("sc_cmajor")
-                _lib.check(lib.eelg_sc_cmajor(ctx.cfg, 0, _lib.ptr(x), n, ctx.mul, _lib.ptr(xt),
-                                              _lib.stream(xt)), "sc_cmajor")
-                _lib.check(lib.eelg_sc_cmajor(ctx.cfg, 1, _lib.ptr(g), n, ctx.mul, _lib.ptr(gt),
-                                              _lib.stream(gt)), "sc_cmajor")
-                TIMER.stop(tok)
+                _sc_cmajor_pair(ctx.cfg, x, g, n, ctx.mul, xt, gt, timed="sc_cmajor")
             chunk = ctx.info["coef_chunk"]          # nodes per streamed (LDS-staged) chunk
             nch = int(lib.eelg_sc_bwd_coef_parts(ctx.cfg, n, ctx.mul))   # partial rows (node ranges)
             part = torch.empty(nch, ctx.mul, ctx.info["coef_ld"], device=x.device, dtype=torch.float32)
@@ -1132,13 +1111,21 @@ class _SymCon(torch.autograd.Function):
                     side.wait_stream(torch.cuda.current_stream(x.device))
                 for t in (xt, gt, part):
                     t.record_stream(side)
-            with torch.cuda.stream(side) if side is not None else _nullctx():
-                tok = TIMER.start("sc_bwd_coef")
-                _lib.check(lib.eelg_sc_bwd_coef(ctx.cfg, _lib.ptr(xt), _lib.ptr(gt), n, ctx.mul,
-                                                chunk, _lib.ptr(part), _lib.stream(part)), "sc_bwd_coef")
-                TIMER.stop(tok)
+            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                _launch("sc_bwd_coef", lib.eelg_sc_bwd_coef, ctx.cfg, xt, gt, n, ctx.mul, chunk, part,
+                        on=part, timed="sc_bwd_coef")
                 gcoef = sum_rows(part)
         return gx, gcoef, None, None, None, None
+
+
+def _sc_cmajor_pair(cfg: int, x, g, n: int, mul: int, xt, gt, timed: Optional[str] = None) -> None:
+    """the channel-major copies ``xt`` of ``x`` and ``gt`` of ``g`` (``eelg_sc_cmajor``, two
+    launches on the current stream under one timer)"""
+    fn = _lib.load().eelg_sc_cmajor
+    tok = TIMER.start(timed) if timed is not None else None
+    for which, src, dst in ((0, x, xt), (1, g, gt)):
+        _launch("sc_cmajor", fn, cfg, which, src, n, mul, dst, on=dst)
+    TIMER.stop(tok)
 
 
 def symmetric_contraction(x, coef, cfg: int, info: Dict[str, int], mul: int, side=None):
@@ -1245,14 +1232,6 @@ def symmetric_contraction_table(x, coef, tab: ScgTable):
     return _SymConTable.apply(x, coef, tab)
 
 
-class _nullctx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
-
-
 # ---------------------------------------------------------------------------
 # radial MLP (conv_tp_weights, gnn/blocks.py:537-549)
 # ---------------------------------------------------------------------------
@@ -1324,6 +1303,31 @@ def _radial_desc(params, n_feat: int):
     return d
 
 
+def _radial_padded(params, n_feat: int, g=None):
+    """(desc, W_o, g, n_out) as the kernels take them: they read the output width in whole 16-B
+    pieces of bf16 (a multiple of 8, as every generated TP weight count is), so another width
+    ``n_out`` runs on zero-padded W_o rows, zero-padded columns of the output gradient ``g`` and
+    ``desc.n_out`` = the padded width"""
+    d = _radial_desc(params, n_feat)
+    wo, n_out = params[-1], d.n_out
+    pad = -n_out % 8
+    if pad:
+        wo = torch.cat([wo, wo.new_zeros(pad, wo.shape[1])])
+        if g is not None:
+            g = torch.cat([g, g.new_zeros(g.shape[0], pad)], 1)
+        d.n_out = n_out + pad
+    return d, wo, g, n_out
+
+
+def _radial_plan(ec: int, n_out: int):
+    """(partial rows of the small-layer gradients, of the W_o gradient) the backward kernels
+    write for ``ec`` edges (``eelg_radial_plan``)"""
+    npart, ns = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().eelg_radial_plan(ec, n_out, ctypes.byref(npart), ctypes.byref(ns)),
+               "radial_plan")
+    return npart.value, ns.value
+
+
 def _radial_chunks(e: int, n_out: int, out_es: int, hidden: int, n_hidden: int):
     """Edge ranges under the radial kernels' 2 GiB per-stream limit (their buffer descriptors
     use 32-bit byte offsets): ``E * n_out * out_es`` for the [E, W] output / its gradient and
@@ -1352,17 +1356,10 @@ class _RadialMLP(torch.autograd.Function):
         feats = _f32(feats)
         params = tuple(_f32(p) for p in params)
         e, nf = feats.shape
-        d = _radial_desc(params, nf)
-        wo = params[-1]
+        d, wo, _, n_out = _radial_padded(params, nf)
         if wo.shape[1] != d.hidden or any(p.shape[0] != d.hidden for p in params[:-1]):
             raise ValueError("radial MLP: hidden widths differ between layers")
-        # the kernels take the output width in whole 16-B pieces of bf16 (a multiple of 8, as every
-        # generated TP weight count is); another width runs on zero-padded W_o rows
-        n_out = d.n_out
-        wp = -(-n_out // 8) * 8
-        if wp != n_out:
-            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
-            d.n_out = wp
+        wp = d.n_out
         out = torch.empty(e, wp, device=feats.device, dtype=out_dtype)
         wo_parts = split_bf16x3(wo)                  # [3, n_out, hidden]: the output layer's B operand
         lib = _lib.load()
@@ -1370,10 +1367,8 @@ class _RadialMLP(torch.autograd.Function):
         zs = []
         for a, b in chunks:
             z = torch.empty(d.n_hidden, b - a, d.hidden, device=feats.device, dtype=torch.float32)
-            _lib.check(lib.eelg_radial_fwd(_lib.ptr(feats[a:b]), b - a, ctypes.byref(d),
-                                           _lib.ptr(wo_parts), int(out_dtype == torch.bfloat16),
-                                           _lib.ptr(z), _lib.ptr(out[a:b]), _lib.stream(feats)),
-                       "radial_fwd")
+            _launch("radial_fwd", lib.eelg_radial_fwd, feats[a:b], b - a, d, wo_parts,
+                    int(out_dtype == torch.bfloat16), z, out[a:b], on=feats)
             zs.append(z)
         ctx.chunks = chunks
         ctx.save_for_backward(feats, *params, *zs)
@@ -1385,14 +1380,7 @@ class _RadialMLP(torch.autograd.Function):
         feats, *rest = ctx.saved_tensors
         params, zs = rest[:ctx.n_params], rest[ctx.n_params:]
         e, nf = feats.shape
-        d = _radial_desc(params, nf)
-        n_out = d.n_out
-        wp = -(-n_out // 8) * 8
-        wo = params[-1]
-        if wp != n_out:                                            # zero-padded width (forward)
-            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
-            g = torch.cat([g, g.new_zeros(g.shape[0], wp - n_out)], 1)
-            d.n_out = wp
+        d, wo, g, n_out = _radial_padded(params, nf, g)
         g = g.contiguous()
         if g.data_ptr() % 16:
             g = g.clone()
@@ -1407,30 +1395,25 @@ class _RadialMLP(torch.autograd.Function):
                 if gfe is None or b == a:
                     continue
                 grad_h = torch.empty(b - a, h, device=g.device, dtype=torch.float32)
-                _lib.check(lib.eelg_radial_bwd_gh(_lib.ptr(g[a:b]), int(g.dtype == torch.bfloat16), b - a,
-                                                  ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(grad_h),
-                                                  _lib.stream(g)), "radial_bwd_gh")
+                _launch("radial_bwd_gh", lib.eelg_radial_bwd_gh, g[a:b], int(g.dtype == torch.bfloat16),
+                        b - a, d, wot_parts, grad_h, on=g)
                 _radial_bwd_x(grad_h, d, z, gfe[a:b])
             return (gfe, None) + (None,) * len(params)
         if RADIAL_CHAIN and h == 64:
-            return _RadialMLP._backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out, gfe)
+            return _RadialMLP._backward_chain(ctx, g, feats, params, zs, d, wot_parts, n_out, gfe)
         n_small = h * nf + h + (d.n_hidden - 1) * (h * h + h)
         small, gwo = None, None
         for (a, b), z in zip(ctx.chunks, zs):
             ec = b - a
-            npart, ns = ctypes.c_int(), ctypes.c_int()
-            _lib.check(lib.eelg_radial_plan(ec, d.n_out, ctypes.byref(npart), ctypes.byref(ns)),
-                       "radial_plan")
-            part_h = torch.empty(npart.value, n_small, device=g.device, dtype=torch.float32)
-            part_wo = torch.empty(ns.value, d.n_out, h, device=g.device, dtype=torch.float32)
+            npart, ns = _radial_plan(ec, d.n_out)
+            part_h = torch.empty(npart, n_small, device=g.device, dtype=torch.float32)
+            part_wo = torch.empty(ns, d.n_out, h, device=g.device, dtype=torch.float32)
             grad_h = torch.empty(ec, h, device=g.device, dtype=torch.float32)
             if ec == 0:
                 part_h.zero_()
                 part_wo.zero_()
-            _lib.check(lib.eelg_radial_bwd(_lib.ptr(g[a:b]), int(g.dtype == torch.bfloat16), ec,
-                                           ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z),
-                                           _lib.ptr(feats[a:b]), _lib.ptr(grad_h), _lib.ptr(part_h),
-                                           _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd")
+            _launch("radial_bwd", lib.eelg_radial_bwd, g[a:b], int(g.dtype == torch.bfloat16), ec, d,
+                    wot_parts, z, feats[a:b], grad_h, part_h, part_wo, on=g)
             if gfe is not None and ec:
                 _radial_bwd_x(grad_h, d, z, gfe[a:b])
             sm, wo = sum_rows(part_h), sum_rows(part_wo)
@@ -1440,56 +1423,65 @@ class _RadialMLP(torch.autograd.Function):
         for p in params[:-1]:
             grads.append(small[off: off + p.numel()].view_as(p))
             off += p.numel()
-        grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
-        return (gfe, None, *grads)
+        return (gfe, None, *grads, _trim_rows(gwo, n_out))
 
     @staticmethod
-    def _backward_chain(ctx, g, feats, params, zs, d, wot_parts, wp, n_out, gfe=None):
-        """``eelg_radial_bwd_chain``: the kernels leave gz_n and the hidden-layer inputs; the
-        weight gradients gz_n^T h_n are long-K reductions on the linear weight-gradient kernel and
-        the bias gradients column sums (``eelg_sum_rows``), all in a fixed order"""
-        from . import dense
-        lib = _lib.load()
-        h, nh = d.hidden, d.n_hidden
-        acc = [None] * (2 * nh)
-        gwo = None
+    def _backward_chain(ctx, g, feats, params, zs, d, wot_parts, n_out, gfe=None):
+        """``_radial_bwd_chain`` per edge range, the ranges' gradients added in range order"""
+        acc = gwo = None
         for (a, b), z in zip(ctx.chunks, zs):
-            ec = b - a
-            npart, ns = ctypes.c_int(), ctypes.c_int()
-            _lib.check(lib.eelg_radial_plan(ec, d.n_out, ctypes.byref(npart), ctypes.byref(ns)),
-                       "radial_plan")
-            part_wo = torch.empty(ns.value, d.n_out, h, device=g.device, dtype=torch.float32)
-            grad_h = torch.empty(ec, h, device=g.device, dtype=torch.float32)
-            gz = torch.empty(nh, ec, h, device=g.device, dtype=torch.float32)
-            hin = torch.empty(max(nh - 1, 1), ec, h, device=g.device, dtype=torch.float32)
-            if ec == 0:
-                part_wo.zero_()
-            _lib.check(lib.eelg_radial_bwd_chain(_lib.ptr(g[a:b]), int(g.dtype == torch.bfloat16), ec,
-                                                 ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z),
-                                                 _lib.ptr(grad_h), _lib.ptr(gz), _lib.ptr(hin),
-                                                 _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd_chain")
-            if gfe is not None and ec:
-                _radial_bwd_x(grad_h, d, z, gfe[a:b])
-            for n in range(nh):
-                x_n = feats[a:b] if n == 0 else hin[n - 1]
-                gw = dense.linear_bwd_w(x_n, gz[n]) if ec else torch.zeros_like(params[2 * n])
-                gb = sum_rows(gz[n]) if ec else torch.zeros_like(params[2 * n + 1])
-                acc[2 * n] = gw if acc[2 * n] is None else acc[2 * n] + gw
-                acc[2 * n + 1] = gb if acc[2 * n + 1] is None else acc[2 * n + 1] + gb
-            wo = sum_rows(part_wo)
+            grads, wo = _radial_bwd_chain(g[a:b], feats[a:b], params, z, d, wot_parts,
+                                          None if gfe is None else gfe[a:b])
+            acc = grads if acc is None else [s + t for s, t in zip(acc, grads)]
             gwo = wo if gwo is None else gwo + wo
-        grads = [t.view_as(p) for t, p in zip(acc, params[:-1])]
-        grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
-        return (gfe, None, *grads)
+        return (gfe, None, *acc, _trim_rows(gwo, n_out))
+
+
+def _trim_rows(gwo, n_out: int):
+    """grad W_o without the rows of a zero-padded width"""
+    return gwo if gwo.shape[0] == n_out else gwo[:n_out].contiguous()
+
+
+def _radial_bwd_chain(g, feats, params, z, d, wot_parts, gfe=None, smap: Optional[StrutMap] = None):
+    """The chain backward of one edge range (hidden 64): ``eelg_radial_bwd_chain`` leaves gz_n and
+    the hidden-layer inputs; the weight gradients gz_n^T h_n are long-K reductions on the linear
+    weight-gradient kernel and the bias gradients column sums (``eelg_sum_rows``), all in a fixed
+    order.  ``g`` [E_c, d.n_out], ``feats`` [E_c, n_feat], ``z`` the saved pre-activations of the
+    range, or with ``smap`` of its shared rows, edge e's at row ``smap.row[e]``
+    (``eelg_radial_bwd_chain_rows``).  ``gfe``: receives the feature gradient.  Returns
+    ([grad w_0, grad b_0, ...], grad W_o of the padded width); zeros for an empty range."""
+    from . import dense
+    lib = _lib.load()
+    ec, h, nh, dev = g.shape[0], d.hidden, d.n_hidden, g.device
+    bf = int(g.dtype == torch.bfloat16)
+    part_wo = torch.empty(_radial_plan(ec, d.n_out)[1], d.n_out, h, device=dev, dtype=torch.float32)
+    grad_h = torch.empty(ec, h, device=dev, dtype=torch.float32)
+    gz = torch.empty(nh, ec, h, device=dev, dtype=torch.float32)
+    hin = torch.empty(max(nh - 1, 1), ec, h, device=dev, dtype=torch.float32)
+    if ec == 0:
+        part_wo.zero_()
+    if smap is None:
+        _launch("radial_bwd_chain", lib.eelg_radial_bwd_chain, g, bf, ec, d, wot_parts, z, grad_h,
+                gz, hin, part_wo, on=g)
+    else:
+        zlast = torch.empty(ec, h, device=dev, dtype=torch.float32)
+        _launch("radial_bwd_chain_rows", lib.eelg_radial_bwd_chain_rows, g, bf, ec, smap.row,
+                smap.n_rows, d, wot_parts, z, grad_h, gz, hin, zlast, part_wo, on=g)
+    if gfe is not None and ec:
+        _radial_bwd_x(grad_h, d, z, gfe)
+    grads = []
+    for n in range(nh):
+        x_n = feats if n == 0 else hin[n - 1]
+        w_n, b_n = params[2 * n], params[2 * n + 1]
+        grads.append(dense.linear_bwd_w(x_n, gz[n]).view_as(w_n) if ec else torch.zeros_like(w_n))
+        grads.append(sum_rows(gz[n]).view_as(b_n) if ec else torch.zeros_like(b_n))
+    return grads, sum_rows(part_wo)
 
 
 def _radial_bwd_x(grad_h, d, z, out) -> None:
     """``eelg_radial_bwd_x`` of one edge chunk: ``out`` [E_c, n_feat] rows of the feature gradient"""
-    tok = TIMER.start("radial_bwd_x")
-    _lib.check(_lib.load().eelg_radial_bwd_x(_lib.ptr(grad_h), grad_h.shape[0], ctypes.byref(d),
-                                             _lib.ptr(z), _lib.ptr(out), _lib.stream(out)),
-               "radial_bwd_x")
-    TIMER.stop(tok)
+    _launch("radial_bwd_x", _lib.load().eelg_radial_bwd_x, grad_h, grad_h.shape[0], d, z, out,
+            on=out, timed="radial_bwd_x")
 
 
 class _RadialMLPShared(torch.autograd.Function):
@@ -1508,21 +1500,14 @@ class _RadialMLPShared(torch.autograd.Function):
         feats_s = smap.rep_rows(feats)               # [S, n_feat]: the only new pass
         params = tuple(_f32(p) for p in params)
         s_rows, nf = feats_s.shape
-        d = _radial_desc(params, nf)
-        wo = params[-1]
-        n_out = d.n_out
-        wp = -(-n_out // 8) * 8
-        if wp != n_out:
-            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
-            d.n_out = wp
+        d, wo, _, n_out = _radial_padded(params, nf)
+        wp = d.n_out
         if d.hidden != 64 or any(p.shape[0] != 64 for p in params[:-1]) or wo.shape[1] != 64:
             raise ValueError("radial MLP on shared rows: hidden width 64 only")
         out = torch.empty(s_rows, wp, device=feats.device, dtype=out_dtype)
         z = torch.empty(d.n_hidden, s_rows, d.hidden, device=feats.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_radial_fwd(
-            _lib.ptr(feats_s), s_rows, ctypes.byref(d), _lib.ptr(split_bf16x3(wo)),
-            int(out_dtype == torch.bfloat16), _lib.ptr(z), _lib.ptr(out), _lib.stream(feats)),
-            "radial_fwd")
+        _launch("radial_fwd", _lib.load().eelg_radial_fwd, feats_s, s_rows, d, split_bf16x3(wo),
+                int(out_dtype == torch.bfloat16), z, out, on=feats)
         token = torch.empty(1, device=feats.device, dtype=torch.float32)
         w = out if wp == n_out else out[:, :n_out].contiguous()
         ctx.box, ctx.smap = box, smap
@@ -1533,46 +1518,16 @@ class _RadialMLPShared(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _gw_unused, _gtoken):
-        from . import dense
         feats, z, *params = ctx.saved_tensors
         g, ctx.box.gw = ctx.box.gw, None
         if g is None:
             raise RuntimeError("radial MLP on shared rows: no weight gradient was handed over "
                                "(the interaction's backward has not run, or ran twice)")
         g.record_stream(torch.cuda.current_stream(g.device))     # made on the TP's stream
-        smap = ctx.smap
-        e, nf = feats.shape
-        d = _radial_desc(params, nf)
-        n_out = d.n_out
-        wp = -(-n_out // 8) * 8
-        wo = params[-1]
-        if wp != n_out:
-            wo = torch.cat([wo, wo.new_zeros(wp - n_out, wo.shape[1])])
-            g = torch.cat([g, g.new_zeros(g.shape[0], wp - n_out)], 1)
-            d.n_out = wp
-        lib = _lib.load()
-        wot_parts = split_bf16x3(wo.t().contiguous())
-        h, nh = d.hidden, d.n_hidden
-        dev = g.device
-        npart, ns = ctypes.c_int(), ctypes.c_int()
-        _lib.check(lib.eelg_radial_plan(e, d.n_out, ctypes.byref(npart), ctypes.byref(ns)), "radial_plan")
-        part_wo = torch.empty(ns.value, d.n_out, h, device=dev, dtype=torch.float32)
-        grad_h = torch.empty(e, h, device=dev, dtype=torch.float32)
-        gz = torch.empty(nh, e, h, device=dev, dtype=torch.float32)
-        hin = torch.empty(max(nh - 1, 1), e, h, device=dev, dtype=torch.float32)
-        zlast = torch.empty(e, h, device=dev, dtype=torch.float32)
-        _lib.check(lib.eelg_radial_bwd_chain_rows(
-            _lib.ptr(g), int(g.dtype == torch.bfloat16), e, _lib.ptr(smap.row), smap.n_rows,
-            ctypes.byref(d), _lib.ptr(wot_parts), _lib.ptr(z), _lib.ptr(grad_h), _lib.ptr(gz),
-            _lib.ptr(hin), _lib.ptr(zlast), _lib.ptr(part_wo), _lib.stream(g)), "radial_bwd_chain_rows")
-        grads = []
-        for n in range(nh):                           # as _RadialMLP._backward_chain, one range
-            x_n = feats if n == 0 else hin[n - 1]
-            grads.append(dense.linear_bwd_w(x_n, gz[n]).view_as(params[2 * n]))
-            grads.append(sum_rows(gz[n]).view_as(params[2 * n + 1]))
-        gwo = sum_rows(part_wo)
-        grads.append(gwo if wp == n_out else gwo[:n_out].contiguous())
-        return (None, None, None, None, *grads)
+        d, wo, g, n_out = _radial_padded(params, feats.shape[1], g)
+        grads, gwo = _radial_bwd_chain(g, feats, params, z, d, split_bf16x3(wo.t().contiguous()),
+                                       smap=ctx.smap)
+        return (None, None, None, None, *grads, _trim_rows(gwo, n_out))
 
 
 def _radial_params(mlp: torch.nn.Sequential) -> list:
@@ -1698,11 +1653,8 @@ class _StiffnessLoss(torch.autograd.Function):
         out = torch.empty(2, device=pred.device, dtype=torch.float32)
         grad = torch.empty_like(p2)
         with torch.cuda.device(pred.device):
-            tok = TIMER.start("stiffness_loss")
-            _lib.check(_lib.load().eelg_stiffness_loss(_lib.ptr(p2), _lib.ptr(t2), nb, n, float(grad_scale),
-                                                       _lib.ptr(out), _lib.ptr(grad), _lib.stream(pred)),
-                       "stiffness_loss")
-            TIMER.stop(tok)
+            _launch("stiffness_loss", _lib.load().eelg_stiffness_loss, p2, t2, nb, n,
+                    float(grad_scale), out, grad, on=pred, timed="stiffness_loss")
         ctx.save_for_backward(grad)
         ctx.shape = pred.shape
         loss, mean = out[0], out[1]

@@ -2,8 +2,8 @@
 
 ``torch.ops.eelg.tp_interaction`` / ``torch.ops.eelg.tp_interaction_bwd`` and
 ``torch.ops.eelg.segment_sum_csr`` are ``torch.library`` custom ops over the same C-ABI
-library the autograd path in ``ops.py`` calls (``eelg_tp_fwd``, ``eelg_tp_bwd`` /
-``eelg_tp_bwd_sender``, ``eelg_segment_sum_csr``).  Each has a fake (meta) kernel, so fx
+library, through the launch paths the autograd functions in ``ops.py`` use (``ops._tp_fwd``,
+``ops._tp_bwd``, ``ops.segment_sum_csr``).  Each has a fake (meta) kernel, so fx
 tracing and ``torch.compile`` see output shapes without running HIP code, and the forward op
 carries its autograd formula.  Reference call site: ``gnn/blocks.py:591-597``
 (``conv_tp(node_feats[sender], edge_attrs, tp_weights)`` + ``scatter(..., receiver) /
@@ -35,7 +35,7 @@ def tp_interaction(x: Tensor, sh: Tensor, w: Tensor, sender: Tensor, receiver: T
                    rowptr: Tensor, sperm: Tensor, srowptr: Tensor, cfg: int,
                    inv_norm: float) -> Tensor:
     csr = _csr(sender, receiver, rowptr, sperm, srowptr)
-    return ops._TPInteraction.forward(_Ctx(), x, sh, w, csr, cfg, _info(cfg), inv_norm)
+    return ops._tp_fwd(x, sh, w, csr, cfg, _info(cfg), inv_norm)[0]
 
 
 @tp_interaction.register_fake
@@ -47,11 +47,10 @@ def _(x, sh, w, sender, receiver, rowptr, sperm, srowptr, cfg, inv_norm):
 def tp_interaction_bwd(g: Tensor, x: Tensor, sh: Tensor, w: Tensor, sender: Tensor,
                        receiver: Tensor, rowptr: Tensor, sperm: Tensor, srowptr: Tensor,
                        cfg: int, inv_norm: float) -> Tuple[Tensor, Tensor]:
-    ctx = _Ctx()
-    ctx.saved_tensors = (x.contiguous(), ops.padded_sh(sh), w.contiguous())
-    ctx.csr, ctx.cfg, ctx.info, ctx.inv_norm = (_csr(sender, receiver, rowptr, sperm, srowptr),
-                                                cfg, _info(cfg), inv_norm)
-    gx, _, gw, *_ = ops._TPInteraction.backward(ctx, g.contiguous())
+    # no SH gradient from the custom ops (``gnn.ops.tp_interaction`` is the entry that has one)
+    gx, _, gw = ops._tp_bwd(x.contiguous(), ops.padded_sh(sh), w.contiguous(),
+                            _csr(sender, receiver, rowptr, sperm, srowptr), cfg, _info(cfg), inv_norm,
+                            g.contiguous())
     return gx, gw
 
 
@@ -105,13 +104,3 @@ def _seg_backward(ctx, g):
 
 segment_sum_csr.register_autograd(_seg_backward, setup_context=_seg_setup)
 
-
-class _Ctx:
-    """Stand-in for an autograd ctx: lets the custom ops reuse ``ops._TPInteraction``'s
-    forward / backward bodies (one launch sequence, not two copies of it).  The ops return no SH
-    gradient (``gnn.ops.tp_interaction`` is the entry that does), so the stand-in asks for none."""
-
-    needs_input_grad = (True, False, True, False, False, False, False)
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts

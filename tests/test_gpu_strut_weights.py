@@ -172,7 +172,8 @@ def _criterion(shared, unshared, ref, name):
     assert es <= 1.5 * eu + 1e-7 * scale, (name, es, eu, scale)
 
 
-@pytest.mark.parametrize("s_rows,n_out", [(1, 160), (33, 1344), (129, 160), (300, 1344)])
+@pytest.mark.parametrize("s_rows,n_out", [(1, 160), (33, 1344), (129, 160), (300, 1344),
+                                          (33, 36)])      # 36: no multiple of 8, zero-padded width
 def test_radial_mlp_shared_rows(s_rows, n_out):
     # S pairs (E = 2S paired edges) and one unpaired edge with a row of its own
     e = 2 * s_rows + 1
