@@ -10,10 +10,11 @@ from .synthetic import SyntheticLattices, make_lattice  # noqa: F401
 from .data import Batch, Data, DataLoader, collate, degree_stats  # noqa: F401
 from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
-from .design import stiffness_sensitivity  # noqa: F401
+from .design import property_sensitivity, stiffness_sensitivity  # noqa: F401
 from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
 from .metrics import (METRIC_COLUMNS, ErrorTable, aggr_errors, evaluate, metric_directions,  # noqa: F401
                       obtain_errors, stiffness_metrics, validation_metrics)
+from .elastic import ELASTIC_COLUMNS, elastic_properties, elastic_properties_composed  # noqa: F401
 from .optim import FlatAdamW  # noqa: F401
 from .trainer import Callback, EarlyStopping, ModelCheckpoint, Trainer  # noqa: F401
 

@@ -106,6 +106,9 @@ _SIGS = {
     "eelg_mandel_rotate": ([_P, _I, _P, _P, _I, _P, _P], _I),
     # validation / test metrics of predicted stiffness matrices
     "eelg_stiffness_metrics": ([_P, _P, _P, _I, _I, _F, _P, _P], _I),
+    # elastic properties of predicted stiffness matrices and their gradient
+    "eelg_elastic_props": ([_P, _P, _I, _I, _P, _P, _P, _P], _I),
+    "eelg_elastic_props_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
     # the tail of the training step: loss + gradient, gradient norm partials, clip + AdamW
     "eelg_stiffness_loss": ([_P, _P, _I, _I, _F, _P, _P, _P], _I),
     "eelg_sqnorm_parts": ([_LL], _I),
@@ -141,6 +144,7 @@ class LinWDesc(ctypes.Structure):
 
 BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
 METRICS_COLS = 16        # include/eelg.h EELG_METRICS_COLS
+ELASTIC_COLS = 12        # include/eelg.h EELG_ELASTIC_COLS
 OPTIM_STATE_COLS = 4     # include/eelg.h EELG_OPTIM_STATE_COLS
 
 

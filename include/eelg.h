@@ -669,6 +669,45 @@ int eelg_mandel_rotate(const float* src, int n_src, const int* sel, const float*
 int eelg_stiffness_metrics(const float* pred, const float* target, const float* dirs, int n_graphs,
                            int n_dirs, float scale, float* out, void* stream);
 
+/* ---- Elastic properties of predicted stiffness matrices and their gradient ------------------
+ * (csrc/eelg_elastic.hip; the arithmetic of one matrix in csrc/eelg_elastic.h)
+ * c [n_graphs, 6, 6] fp32 Mandel, dirs [n_dirs, 3] unit vectors (NULL with n_dirs == 0).  The
+ * function is defined on the symmetric part A = (C + C^T) / 2 (both triangles are read), S = A^-1
+ * by a Cholesky factorisation in fp64 inside the kernel.  a, b, c of a matrix: the sums of its
+ * three normal diagonal entries, its three normal off-diagonal entries (one triangle) and its three
+ * shear diagonal entries.  Row of graph g in props [n_graphs, EELG_ELASTIC_COLS]:
+ *   0 K_V   (a_A + 2 b_A) / 9                    1 G_V   (a_A - b_A + 1.5 c_A) / 15
+ *   2 K_R   1 / (a_S + 2 b_S)                    3 G_R   15 / (4 a_S - 4 b_S + 6 c_S)
+ *   4 K_H   (K_V + K_R) / 2                      5 G_H   (G_V + G_R) / 2
+ *   6 E_H   9 K_H G_H / (3 K_H + G_H)            7 nu_H  (3 K_H - 2 G_H) / (2 (3 K_H + G_H))
+ *   8 A_U   5 G_V / G_R + K_V / K_R - 6
+ *   9 E_min, 10 E_max   the extremes of e_dir's row (NaN with n_dirs == 0); on a tie the first
+ *                       direction is the extreme, also for the gradient
+ *   11 spd  1.0 if every pivot of the factorisation is finite and > 0, else 0.0
+ * e_dir [n_graphs, n_dirs]: E_p = 1 / (m_p^T S m_p), m = (d1^2, d2^2, d3^2, r2 d2 d3, r2 d1 d3,
+ * r2 d1 d2).  s [n_graphs, 6, 6]: the compliance, kept for the backward.  A graph with spd == 0 has
+ * K_V and G_V only: its other columns, its e_dir row and its s are NaN.
+ *
+ * eelg_elastic_props_bwd: g_c [n_graphs, 6, 6] (exactly symmetric) from the cotangents g_props
+ * [n_graphs, EELG_ELASTIC_COLS] and g_e_dir [n_graphs, n_dirs] (NULL: zero) and the forward's s,
+ * e_dir and props: the direct terms of K_V and G_V plus -S G_S S, G_S collecting the a, b, c terms
+ * of the Reuss / Hill / A_U columns and -E_p^2 m m^T per direction (E_min / E_max on their first
+ * extreme).  The spd column has no gradient.  A graph with spd == 0 gets the Voigt terms alone: the
+ * cotangents of its NaN columns are not read, so they contribute exactly zero.
+ *
+ * One wavefront per graph, directions strided over the lanes, fixed xor butterflies (sums, and
+ * (value, index) pairs for the extremes); no LDS, scratch or atomics.  A graph's row and gradient
+ * depend on (its matrix, dirs, n_dirs, its cotangents) alone: bitwise equal in any batch, at any
+ * position, on every run.
+ * n_graphs == 0: nothing is launched, 0 is returned whatever the pointers.  -2: n_graphs < 0,
+ * n_dirs < 0, a null pointer (dirs, e_dir: only with n_dirs > 0). */
+#define EELG_ELASTIC_COLS 12
+int eelg_elastic_props(const float* c, const float* dirs, int n_graphs, int n_dirs, float* props,
+                       float* e_dir, float* s, void* stream);
+int eelg_elastic_props_bwd(const float* s, const float* dirs, const float* e_dir, const float* props,
+                           const float* g_props, const float* g_e_dir, int n_graphs, int n_dirs,
+                           float* g_c, void* stream);
+
 /* ---- The tail of the training step: loss, gradient norm, clip + AdamW --------------------------
  * (csrc/eelg_optim.hip; per-element arithmetic in csrc/eelg_adamw.h)
  *
