@@ -10,7 +10,9 @@ from .synthetic import SyntheticLattices, make_lattice  # noqa: F401
 from .data import Batch, Data, DataLoader, collate, degree_stats  # noqa: F401
 from .train import LightningWrappedModel, stiffness_loss  # noqa: F401
 from .lattice_data import GLAMM_Dataset, RotateLat, process_lattice  # noqa: F401
-from .design import property_sensitivity, stiffness_sensitivity  # noqa: F401
+from .design import (DesignLayout, DesignResult, design_layout, design_step, design_step_composed,  # noqa: F401
+                     optimize_design, property_sensitivity, stiffness_sensitivity, strut_volume,
+                     strut_volume_composed)
 from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
 from .metrics import (METRIC_COLUMNS, ErrorTable, aggr_errors, evaluate, metric_directions,  # noqa: F401
                       obtain_errors, stiffness_metrics, validation_metrics)

@@ -114,6 +114,9 @@ _SIGS = {
     "eelg_sqnorm_parts": ([_LL], _I),
     "eelg_grad_sqnorm": ([_P, _LL, _P, _P], _I),
     "eelg_adamw_flat": ([_P, _P, _P, _P, _P, _LL, _P, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P], _I),
+    # lattice design: strut volume per graph, and the tail of a design iteration in one launch
+    "eelg_strut_volume": ([_P] * 9 + [_I, _I, _I, _P, _P], _I),
+    "eelg_design_step": ([_P] * 16 + [_I, _I, _I] + [_F] * 6 + [_I, _P, _P, _P], _I),
 }
 
 LIN_MAXSRC, LIN_MAXSLOT, LINW_MAXINS = 4, 8, 8
@@ -146,6 +149,7 @@ BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
 METRICS_COLS = 16        # include/eelg.h EELG_METRICS_COLS
 ELASTIC_COLS = 12        # include/eelg.h EELG_ELASTIC_COLS
 OPTIM_STATE_COLS = 4     # include/eelg.h EELG_OPTIM_STATE_COLS
+DESIGN_THREADS = 256     # include/eelg.h EELG_DESIGN_THREADS
 
 
 class BatchSrc(ctypes.Structure):

@@ -754,6 +754,61 @@ int eelg_adamw_flat(float* p, float* m, float* v, float* vmax, float* grad, long
                     double weight_decay, double max_norm, int amsgrad, const int* state_in, int* state_out,
                     void* stream);
 
+/* ---- Gradient-based lattice design: strut volume and the design step ----------------------------
+ * (csrc/eelg_design.hip; per-element arithmetic in csrc/eelg_design.h)
+ * A batch of n_graphs lattices in the caller's node / edge order: pos [n_nodes, 3], r [n_edges]
+ * (strut radii, every strut listed in both directions), shifts [n_edges, 3], send / recv [n_edges]
+ * int32 (batch-global node rows), node_ptr / edge_ptr [n_graphs + 1] int32 on the device: graph g
+ * owns the nodes node_ptr[g] .. node_ptr[g + 1] and the edges edge_ptr[g] .. edge_ptr[g + 1] (a
+ * graph's edges are contiguous).  node_ptr_host / edge_ptr_host: the same two rows in host memory;
+ * a launch cannot read device memory without waiting for the device, so these are what it checks
+ * (-2 unless each starts at 0, never decreases and ends at n_nodes / n_edges).  The kernels cut
+ * the device rows to the arrays and refuse a graph whose send / recv (or partner) leave its own
+ * rows, so a device row that disagrees with its mirror gives that graph NaN (and
+ * EELG_DESIGN_BAD_INDEX), never an access outside the arrays.
+ *
+ * eelg_strut_volume: vol[g] = 1/2 sum over the directed edges e of g of r_e^2 L_e, L_e =
+ * |(pos[recv] - pos[send]) + shift_e| with the vector formed in fp32 as eelg_edge_embed forms it;
+ * pi and the cell volume are constant for a fixed cell, so this is the relative density up to a
+ * factor.  Terms and sum in fp64 in a fixed order, rounded to fp32 once.  Forward only.
+ *
+ * eelg_design_step: the tail of one design iteration, in place on pos, r and the momenta m_pos
+ * [n_nodes, 3], m_r [n_edges], from the gradients g_pos, g_r of the objective to minimise.
+ * partner [n_edges] int32, caller order: the edge that is the other direction of the same strut,
+ * or the edge itself.  pos0: the initial positions.  v0 [n_graphs]: the volume to keep.  Per graph:
+ *   1. g~_r[e] = g_r[e] + g_r[partner[e]] (partner[e] != e), else g_r[e]: bitwise equal in both
+ *      directions of a strut.
+ *   2. If any g~_r or g_pos of the graph is Inf or NaN: nothing of the graph changes, flag[g] =
+ *      EELG_DESIGN_NONFINITE (1), vol[g] = its current volume.
+ *   3. G_r = max |g~_r|, G_p = max |g_pos| over the graph.  A group (radii, positions) whose
+ *      maximum is 0 or whose step size is 0 is left as it is, momentum included.
+ *   4. m_r = beta m_r + g~_r / G_r, r = clamp(r - step_r m_r, r_min, r_max); m_pos = beta m_pos +
+ *      g_pos / G_p, pos = clamp(pos - step_pos m_pos, pos0 - move_limit, pos0 + move_limit) per
+ *      component.  step_* is the largest move of an iteration from rest, in length units.
+ *   5. V of the new geometry; with keep_volume, r = clamp(r sqrt(v0 / V), r_min, r_max) in one
+ *      pass and V again.  Where a clamp binds V may miss v0; that is not iterated.  A v0 or V that
+ *      is not a positive finite number leaves the radii unscaled.
+ *   6. vol[g] = V, flag[g] = 0.
+ * Struts that arrive with bitwise-equal radii and momenta in both directions leave that way.
+ * One workgroup of EELG_DESIGN_THREADS threads per graph; a graph's outputs depend on its own rows
+ * alone: bitwise equal in any batch, at any position, on every run.  No atomics, no scratch, LDS
+ * for the reduction slots only.
+ * -2: n_graphs < 1, negative sizes, a null pointer, ptr rows that fail the check above, r_min >=
+ * r_max, move_limit < 0.  n_edges == 0: eelg_design_step launches nothing (0 is returned, vol and
+ * flag are not written); eelg_strut_volume stores zeros. */
+#define EELG_DESIGN_THREADS 256
+int eelg_strut_volume(const float* pos, const float* r, const float* shifts, const int* send,
+                      const int* recv, const int* node_ptr, const int* edge_ptr,
+                      const int* node_ptr_host, const int* edge_ptr_host, int n_graphs, int n_nodes,
+                      int n_edges, float* vol, void* stream);
+int eelg_design_step(const float* g_pos, const float* g_r, float* pos, float* r, const float* pos0,
+                     float* m_pos, float* m_r, const int* partner, const int* node_ptr,
+                     const int* edge_ptr, const int* node_ptr_host, const int* edge_ptr_host,
+                     const float* shifts, const int* send, const int* recv, const float* v0,
+                     int n_graphs, int n_nodes, int n_edges, float step_r, float step_pos, float beta,
+                     float r_min, float r_max, float move_limit, int keep_volume, float* vol, int* flag,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
