@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch  # noqa: F401  (loads torch's libamdhip64 first; the .so binds to it by SONAME)
 
@@ -243,6 +243,53 @@ def stream(t: torch.Tensor) -> ctypes.c_void_p:
         raise EELGError(f"operand on {dev} but the current HIP device is cuda:{cur}; run the "
                         f"model under torch.cuda.device({dev.index}) or set_device({dev.index})")
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class KernelTimer:
+    """Optional HIP-event timing of selected launches (used by ``bench.py``).
+
+    Events are recorded on the current stream, the one every op launches on."""
+
+    def __init__(self):
+        self.enabled = False
+        self.records: Dict[str, list] = {}
+
+    def start(self, name: str):
+        if not self.enabled:
+            return None
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return (name, ev)
+
+    def stop(self, tok) -> None:
+        if tok is None:
+            return
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        self.records.setdefault(tok[0], []).append((tok[1], ev))
+
+    def summary(self) -> Dict[str, Dict[str, float]]:
+        torch.cuda.synchronize()
+        out = {}
+        for name, pairs in self.records.items():
+            ms = [a.elapsed_time(b) for a, b in pairs]
+            out[name] = {"count": len(ms), "mean_ms": sum(ms) / len(ms), "total_ms": sum(ms)}
+        return out
+
+
+TIMER = KernelTimer()
+
+
+def launch(name: str, fn, *args, on: torch.Tensor, timed: Optional[str] = None) -> None:
+    """``fn(*args, stream)`` on the current stream of ``on``'s device, checked under the error
+    label ``name``; ``timed``: the ``TIMER`` label of the launch.  Tensors and None pass as
+    addresses, ctypes structures by reference, numbers and raw addresses as they are; dtype,
+    layout and alignment are the caller's."""
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor)
+            else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args]
+    tok = TIMER.start(timed) if timed is not None else None
+    check(fn(*argv, stream(on)), name)
+    TIMER.stop(tok)
 
 
 def tp_config(name: str) -> Tuple[int, Dict[str, int], int]:

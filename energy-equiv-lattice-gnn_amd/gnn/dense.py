@@ -12,16 +12,13 @@ address a column block of a wider weight (the sender / receiver / edge blocks of
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, o3, ops
 
-LINW_WG = 4096          # weight-gradient workgroups (node slices x 32x32 tiles), as o3.Linear
-LINW_MAX_SLICES = 128
 # forward / grad-x with K in [LIN_X6_MINK, 320] (whole 32-wide chunks, n_out % 32 == 0) on the
 # fp32-accurate split-bf16 packed kernel (eelg_linear_fwd_pk), the weight packed per call
 # (~7 us; the CGC layer's [W_v; W_m] is a fresh concatenation every forward, so a cache keyed
@@ -52,23 +49,6 @@ def _slot_desc(n_out: int, k: int, w_off: int, ldk: int, ldj: int, bias: bool, n
     return d
 
 
-def _x6(x, w, bias, res, n, y, n_out, k, desc) -> bool:
-    from .o3 import LIN_X6_MINK
-    if not (DENSE_X6 and k % 32 == 0 and LIN_X6_MINK <= k <= 320 and n_out % 32 == 0
-            and x.shape[1] % 4 == 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0
-            and (res is None or res.data_ptr() % 16 == 0)):
-        return False
-    lib = _lib.load()
-    pk = torch.empty(3, int(lib.eelg_linear_pack_size(ctypes.byref(desc))), device=w.device,
-                     dtype=torch.bfloat16)
-    _lib.check(lib.eelg_linear_pack(_lib.ptr(w), ctypes.byref(desc), _lib.ptr(pk), _lib.stream(pk)),
-               "dense_pack")
-    _lib.check(lib.eelg_linear_fwd_pk(
-        _lib.ptr(x), x.shape[1], _lib.ptr(pk), _lib.ptr(bias), _lib.ptr(res), n, _lib.ptr(y), n_out,
-        ctypes.byref(desc), _lib.stream(y)), "dense_fwd_pk")
-    return True
-
-
 def linear_fwd(x: torch.Tensor, w: torch.Tensor, n_out: int, k: int, w_off: int = 0,
                ld: Optional[int] = None, bias: Optional[torch.Tensor] = None,
                res: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -77,12 +57,8 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, n_out: int, k: int, w_off: int 
     ld = k if ld is None else ld
     n = x.shape[0]
     y = torch.empty(n, n_out, device=x.device, dtype=torch.float32)
-    desc = _slot_desc(n_out, k, w_off, 1, ld, bias is not None, n)
-    if _x6(x, w, bias, res, n, y, n_out, k, desc):
-        return y
-    _lib.check(_lib.load().eelg_linear_fwd_res(
-        _lib.ptr(x), x.shape[1], _lib.ptr(w), _lib.ptr(bias), _lib.ptr(res), n, _lib.ptr(y), n_out,
-        ctypes.byref(desc), _lib.stream(y)), "dense_fwd")
+    o3.linear_apply("dense", "dense_fwd", _slot_desc(n_out, k, w_off, 1, ld, bias is not None, n),
+                    DENSE_X6, x, x.shape[1], w, bias, res, n, y, n_out)
     return y
 
 
@@ -92,12 +68,8 @@ def linear_bwd_x(gy: torch.Tensor, w: torch.Tensor, n_out: int, k: int, w_off: i
     ld = k if ld is None else ld
     n = gy.shape[0]
     gx = torch.empty(n, k, device=gy.device, dtype=torch.float32)
-    desc = _slot_desc(k, n_out, w_off, ld, 1, False, n)
-    if _x6(gy, w, None, res, n, gx, k, n_out, desc):
-        return gx
-    _lib.check(_lib.load().eelg_linear_fwd_res(
-        _lib.ptr(gy), gy.shape[1], _lib.ptr(w), None, _lib.ptr(res), n, _lib.ptr(gx), k,
-        ctypes.byref(desc), _lib.stream(gx)), "dense_bwd_x")
+    o3.linear_apply("dense", "dense_bwd_x", _slot_desc(k, n_out, w_off, ld, 1, False, n),
+                    DENSE_X6, gy, gy.shape[1], w, None, res, n, gx, k)
     return gx
 
 
@@ -117,23 +89,15 @@ def linear_bwd_w(x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
         tps = max(1, -(-ntile // max(1, LINW_X6_WG // nblk)))
         splits = -(-ntile // tps)
         part = torch.empty(splits, n_out * k, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_linear_bwd_w_x6(
-            _lib.ptr(gy), gy.stride(0), _lib.ptr(x), x.stride(0), n, n_out, k, tps, _lib.ptr(part),
-            _lib.stream(part)), "dense_bwd_w_x6")
+        _lib.launch("dense_bwd_w_x6", _lib.load().eelg_linear_bwd_w_x6, gy, gy.stride(0), x,
+                    x.stride(0), n, n_out, k, tps, part, on=part)
         return ops.sum_rows(part).view(n_out, k)
-    tiles = ((k + 31) // 32) * ((n_out + 31) // 32)
-    slices = max(1, min((n + 31) // 32, -(-LINW_WG // tiles), LINW_MAX_SLICES))
-    nps = -(-n // slices)
-    slices = -(-n // nps)
     wd = _lib.LinWDesc()
     wd.n_ins, wd.max_jt, wd.max_ut, wd.max_rows = 1, (n_out + 31) // 32, (k + 31) // 32, n
     e = wd.ins[0]
     e.x_off, e.k, e.g_off, e.n_out, e.d, e.w_off, e.alpha = 0, k, 0, n_out, 1, 0, 1.0
-    part = torch.empty(slices, k * n_out, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().eelg_linear_bwd_w(
-        _lib.ptr(x), k, _lib.ptr(gy), n_out, n, nps, _lib.ptr(part), slices, k * n_out,
-        ctypes.byref(wd), _lib.stream(part)), "dense_bwd_w")
-    return ops.sum_rows(part).view(k, n_out).t()
+    gw = o3.linear_bwd_w("dense_bwd_w", wd, x, k, gy, n_out, n, wd.max_ut * wd.max_jt, k * n_out)
+    return gw.view(k, n_out).t()
 
 
 class _DenseFn(torch.autograd.Function):

@@ -256,13 +256,12 @@ def strut_volume(batch, layout: Optional[DesignLayout] = None) -> torch.Tensor:
 
 
 def _volume_fused(pos, r, shifts, layout: DesignLayout, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    from .ops import _launch
     vol = torch.empty(layout.n_graphs, dtype=torch.float32, device=pos.device) if out is None else out
     with torch.cuda.device(pos.device):
-        _launch("strut_volume", _lib.load().eelg_strut_volume, pos, r, shifts, layout.send, layout.recv,
-                layout.node_ptr, layout.edge_ptr, ctypes.addressof(layout.host_node_ptr),
-                ctypes.addressof(layout.host_edge_ptr), layout.n_graphs, layout.n_nodes, layout.n_edges, vol,
-                on=vol, timed="strut_volume")
+        _lib.launch("strut_volume", _lib.load().eelg_strut_volume, pos, r, shifts, layout.send, layout.recv,
+                     layout.node_ptr, layout.edge_ptr, ctypes.addressof(layout.host_node_ptr),
+                     ctypes.addressof(layout.host_edge_ptr), layout.n_graphs, layout.n_nodes, layout.n_edges, vol,
+                     on=vol, timed="strut_volume")
     return vol
 
 
@@ -360,7 +359,6 @@ def design_step(layout: DesignLayout, g_pos, g_r, pos, r, pos0, m_pos, m_r, shif
         ret_vol = out[4] if vol is None else vol.copy_(out[4])
         ret_flag = out[5] if flag is None else flag.copy_(out[5])
         return pos, r, m_pos, m_r, ret_vol, ret_flag
-    from .ops import _launch
     _check_step(layout, g_pos, g_r, pos, r, pos0, m_pos, m_r, shifts, v0, r_min, r_max, move_limit, "design_step")
     if pos.dtype != torch.float32:
         raise ValueError(f"design_step: the fused step is fp32, got {pos.dtype}")
@@ -376,12 +374,12 @@ def design_step(layout: DesignLayout, g_pos, g_r, pos, r, pos0, m_pos, m_r, shif
             or flag.dtype != torch.int32:
         raise ValueError(f"design_step: vol / flag must be [{nb}] float32 / int32")
     with torch.cuda.device(pos.device):
-        _launch("design_step", _lib.load().eelg_design_step, g_pos.contiguous(), g_r.contiguous(), pos, r,
-                pos0.contiguous(), m_pos, m_r, layout.partner, layout.node_ptr, layout.edge_ptr,
-                ctypes.addressof(layout.host_node_ptr), ctypes.addressof(layout.host_edge_ptr), shifts.contiguous(),
-                layout.send, layout.recv, v0.contiguous(), nb, layout.n_nodes, layout.n_edges, float(step_r),
-                float(step_pos), float(beta), float(r_min), float(r_max), float(move_limit), int(bool(keep_volume)),
-                vol, flag, on=pos, timed="design_step")
+        _lib.launch("design_step", _lib.load().eelg_design_step, g_pos.contiguous(), g_r.contiguous(), pos, r,
+                     pos0.contiguous(), m_pos, m_r, layout.partner, layout.node_ptr, layout.edge_ptr,
+                     ctypes.addressof(layout.host_node_ptr), ctypes.addressof(layout.host_edge_ptr), shifts.contiguous(),
+                     layout.send, layout.recv, v0.contiguous(), nb, layout.n_nodes, layout.n_edges, float(step_r),
+                     float(step_pos), float(beta), float(r_min), float(r_max), float(move_limit), int(bool(keep_volume)),
+                     vol, flag, on=pos, timed="design_step")
     return pos, r, m_pos, m_r, vol, flag
 
 

@@ -255,7 +255,6 @@ class DeviceLoader:
         """The collated batch of the graphs ``graph_ids`` (host integers; repeats allowed), each
         rotated by its ``Q`` (``[B, 3, 3]``, or one ``[3, 3]`` for all; host or device, any float
         dtype, used in fp32) or left as stored when ``Q`` is ``None``."""
-        from .ops import _launch
         dds = self.dds
         dev = dds.device
         if dev.type != "cuda":
@@ -337,11 +336,11 @@ class DeviceLoader:
             setattr(out, k, b.csr[k].data_ptr() or None)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            _launch("batch_assemble", lib.eelg_batch_assemble, self._source(), sdev, q_dev, nb, n_nodes,
-                    n_edges, out, on=b.positions, timed="batch_assemble")
+            _lib.launch("batch_assemble", lib.eelg_batch_assemble, self._source(), sdev, q_dev, nb, n_nodes,
+                         n_edges, out, on=b.positions, timed="batch_assemble")
             sel = sdev[4 * ld:o_rel]
             for key in ("stiffness", "compliance"):
                 if key in t:
-                    _launch("mandel_rotate", lib.eelg_mandel_rotate, t[key], len(dds), sel, q_dev, nb,
-                            getattr(b, key), on=b.positions, timed="mandel_rotate")
+                    _lib.launch("mandel_rotate", lib.eelg_mandel_rotate, t[key], len(dds), sel, q_dev, nb,
+                                 getattr(b, key), on=b.positions, timed="mandel_rotate")
         return b

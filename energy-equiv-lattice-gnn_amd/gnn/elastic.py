@@ -117,7 +117,6 @@ def elastic_properties_composed(c: torch.Tensor, directions: Optional[torch.Tens
 class _ElasticProps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c, directions):
-        from .ops import _launch
         nb = int(c.shape[0])
         n_dirs = 0 if directions is None else int(directions.shape[0])
         c32 = c.detach().to(torch.float32).contiguous()
@@ -126,8 +125,8 @@ class _ElasticProps(torch.autograd.Function):
         e_dir = torch.empty((nb, n_dirs), dtype=torch.float32, device=c.device)
         s = torch.empty((nb, 6, 6), dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
-            _launch("elastic_props", _lib.load().eelg_elastic_props, c32, d32, nb, n_dirs, props,
-                    e_dir if n_dirs else None, s, on=c32, timed="elastic_props")
+            _lib.launch("elastic_props", _lib.load().eelg_elastic_props, c32, d32, nb, n_dirs, props,
+                         e_dir if n_dirs else None, s, on=c32, timed="elastic_props")
         ctx.save_for_backward(s, d32, e_dir, props)
         ctx.in_dtype = c.dtype
         return props, e_dir
@@ -135,7 +134,6 @@ class _ElasticProps(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_props, g_e_dir):
-        from .ops import _launch
         s, d32, e_dir, props = ctx.saved_tensors
         nb, n_dirs = int(e_dir.shape[0]), int(e_dir.shape[1])
         if g_props is None:
@@ -145,9 +143,9 @@ class _ElasticProps(torch.autograd.Function):
             g_e_dir = g_e_dir.to(torch.float32).contiguous()
         g_c = torch.empty((nb, 6, 6), dtype=torch.float32, device=s.device)
         with torch.cuda.device(s.device):
-            _launch("elastic_props_bwd", _lib.load().eelg_elastic_props_bwd, s, d32,
-                    e_dir if n_dirs else None, props, g_props, g_e_dir if n_dirs else None, nb, n_dirs, g_c,
-                    on=s, timed="elastic_props_bwd")
+            _lib.launch("elastic_props_bwd", _lib.load().eelg_elastic_props_bwd, s, d32,
+                         e_dir if n_dirs else None, props, g_props, g_e_dir if n_dirs else None, nb, n_dirs, g_c,
+                         on=s, timed="elastic_props_bwd")
         return g_c.to(ctx.in_dtype), None
 
 

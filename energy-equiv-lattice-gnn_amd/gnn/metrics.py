@@ -104,15 +104,14 @@ def stiffness_metrics(pred: torch.Tensor, target: torch.Tensor, directions: torc
             return rows
         out.copy_(rows)
         return out
-    from .ops import _launch
     pred = pred.to(torch.float32).contiguous()
     target = target.to(torch.float32).contiguous()
     directions = directions.to(torch.float32).contiguous()
     if out is None:
         out = torch.empty((nb, len(METRIC_COLUMNS)), dtype=torch.float32, device=target.device)
     with torch.cuda.device(target.device):
-        _launch("stiffness_metrics", _lib.load().eelg_stiffness_metrics, pred, target, directions, nb,
-                int(directions.shape[0]), float(scale), out, on=target, timed="stiffness_metrics")
+        _lib.launch("stiffness_metrics", _lib.load().eelg_stiffness_metrics, pred, target, directions, nb,
+                     int(directions.shape[0]), float(scale), out, on=target, timed="stiffness_metrics")
     return out
 
 

@@ -14,11 +14,11 @@ import ctypes
 import math
 import os
 from collections import Counter
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
-from . import cg
+from . import _lib, cg, ops
 from .irreps import Irreps
 
 # grad-W launch shape: target workgroups and a cap on the node slices (partials)
@@ -36,6 +36,82 @@ LIN_X6 = os.environ.get("EELG_LIN_X6", "1") != "0"
 LIN_X6_MINK = int(os.environ.get("EELG_LIN_X6_MINK", "128"))
 # the readout Gate as fused HIP passes (1) or torch elementwise ops (0)
 GATE_FUSED = os.environ.get("EELG_GATE_FUSED", "1") != "0"
+
+
+# ---------------------------------------------------------------------------
+# launch helpers of the eelg_linear_* kernels, shared by this module's Linear and dense.Linear
+# ---------------------------------------------------------------------------
+def linw_slices(n: int, tiles: int) -> Tuple[int, int]:
+    """The grad-W node slices of ``n`` rows over ``tiles`` 32x32 weight tiles: (slices, nodes per
+    slice) for ~LINW_WG workgroups in total, (node slices) x (tiles); each slice leaves one
+    partial weight gradient that the sum reads back."""
+    slices = max(1, min((n + 31) // 32, -(-LINW_WG // tiles), LINW_MAX_SLICES))
+    nps = -(-n // slices)
+    return -(-n // nps), nps
+
+
+def linear_bwd_w(label: str, desc, x, x_row: int, gy, gy_row: int, n: int, tiles: int, numel: int,
+                 covers: bool = True) -> torch.Tensor:
+    """``eelg_linear_bwd_w`` over the slices of ``linw_slices`` and the fixed-order sum of its
+    partials, flat [numel].  ``covers``: the descriptor writes every entry (else they start 0)."""
+    slices, nps = linw_slices(n, tiles)
+    part = (torch.empty if covers else torch.zeros)(slices, numel, device=x.device, dtype=torch.float32)
+    _lib.launch(label, _lib.load().eelg_linear_bwd_w, x, x_row, gy, gy_row, n, nps, part, slices,
+                numel, desc, on=part)
+    return ops.sum_rows(part)
+
+
+def packable(desc) -> bool:
+    """the descriptor qualifies for eelg_linear_fwd_pk (whole 32-wide K chunks and column
+    tiles, d odd <= 9, 16-B aligned slot offsets; the row alignment is checked per call)"""
+    for s in range(desc.n_slots):
+        sl = desc.slot[s]
+        if sl.n_src == 0 or sl.n_out % 32 or sl.y_off % 4 or sl.d not in (1, 3, 5, 7, 9):
+            return False
+        if sl.bias_off >= 0 and sl.d != 1:
+            return False
+        ks = sum(sl.src[t].k for t in range(sl.n_src))
+        if ks > 320 or ks < LIN_X6_MINK:
+            return False
+        for t in range(sl.n_src):
+            if sl.src[t].k % 32 or sl.src[t].x_off % 4:
+                return False
+    return True
+
+
+def takes_packed(desc, switch: bool, x_row: int, out_row: int, x_at: int, out_at: int,
+                 res_at: Optional[int] = None, desc_ok: Optional[bool] = None) -> bool:
+    """A call runs on eelg_linear_fwd_pk: the switch is on, the descriptor is ``packable``
+    (``desc_ok``: that answer where the caller keeps it), rows are whole float4, the operands at
+    addresses ``x_at`` / ``out_at`` / ``res_at`` are 16-B aligned and an added operand has the
+    output's own rows."""
+    return bool(switch and x_row % 4 == 0 and out_row % 4 == 0 and x_at % 16 == 0 and out_at % 16 == 0
+                and (res_at is None or (res_at % 16 == 0 and desc.res_row == 0))
+                and (packable(desc) if desc_ok is None else desc_ok))
+
+
+def pack_weights(label: str, desc, weight) -> torch.Tensor:
+    """the split, alpha-scaled bf16 weights of ``desc`` in the packed kernel's layout"""
+    lib = _lib.load()
+    pk = torch.empty(3, int(lib.eelg_linear_pack_size(ctypes.byref(desc))), device=weight.device,
+                     dtype=torch.bfloat16)
+    _lib.launch(label, lib.eelg_linear_pack, weight, desc, pk, on=pk)
+    return pk
+
+
+def linear_apply(prefix: str, label: str, desc, switch: bool, x, x_row: int, weight, bias, res,
+                 n: int, out, out_row: int, desc_ok: Optional[bool] = None, packed=None) -> None:
+    """``out = x B (+ bias) (+ res)`` over ``desc``: the packed kernel where ``takes_packed``
+    (labels ``prefix``_pack / ``prefix``_fwd_pk), else ``eelg_linear_fwd_res`` under ``label``.
+    ``packed()`` hands over the packed weights a caller caches; None packs them on this call."""
+    if takes_packed(desc, switch, x_row, out_row, x.data_ptr(), out.data_ptr(),
+                    None if res is None else res.data_ptr(), desc_ok):
+        pk = packed() if packed is not None else pack_weights(prefix + "_pack", desc, weight)
+        _lib.launch(prefix + "_fwd_pk", _lib.load().eelg_linear_fwd_pk, x, x_row, pk, bias, res, n,
+                    out, out_row, desc, on=out)
+    else:
+        _lib.launch(label, _lib.load().eelg_linear_fwd_res, x, x_row, weight, bias, res, n, out,
+                    out_row, desc, on=out)
 
 
 def _output_mask(irreps_out, covered) -> torch.Tensor:
@@ -198,7 +274,6 @@ class _LinearKernels:
 
     # -- descriptor tables for the C ABI (built by _set_pieces) ------------------
     def _build_descriptors(self):
-        from . import _lib
         w_offs, off = {}, 0
         for i, o in self.instructions:
             w_offs[(i, o)] = off
@@ -283,7 +358,6 @@ class _LinearKernels:
     def _bx_desc_with(self, pieces):
         """the grad-x descriptor for an added gradient in compact rows of ``pieces`` (pieces of
         this linear's input irreps): slots the pieces do not cover add nothing"""
-        from . import _lib
         hit = self._bx_res.get(pieces)
         if hit is not None:
             return hit
@@ -299,58 +373,24 @@ class _LinearKernels:
         self._bx_res[pieces] = (desc, width)
         return desc, width
 
-    @staticmethod
-    def _packable(desc) -> bool:
-        """the descriptor qualifies for eelg_linear_fwd_pk (whole 32-wide K chunks and column
-        tiles, d odd <= 9, 16-B aligned slot offsets; the row alignment is checked per call)"""
-        for s in range(desc.n_slots):
-            sl = desc.slot[s]
-            if sl.n_src == 0 or sl.n_out % 32 or sl.y_off % 4 or sl.d not in (1, 3, 5, 7, 9):
-                return False
-            if sl.bias_off >= 0 and sl.d != 1:
-                return False
-            ks = sum(sl.src[t].k for t in range(sl.n_src))
-            if ks > 320 or ks < LIN_X6_MINK:
-                return False
-            for t in range(sl.n_src):
-                if sl.src[t].k % 32 or sl.src[t].x_off % 4:
-                    return False
-        return True
+    _packable = staticmethod(packable)
 
     def _packed(self, which: str, weight):
         """split, alpha-scaled weights of descriptor ``which`` ('fwd' or 'bx') for the packed
         kernel, rebuilt when the weight changes (cached per weight version).  A write through
         ``weight.data`` does not bump the version counter: such writers call
         ``invalidate_packed()`` (``parallel.broadcast_parameters`` and ``load_state_dict`` do)."""
-        from . import _lib
         key = (weight.data_ptr(), weight._version, weight.device)
         hit = self._pk_cache.get(which)
         if hit is not None and hit[0] == key:
             return hit[1]
         desc = self._fwd_desc if which == "fwd" else self._bx_desc
-        n = int(_lib.load().eelg_linear_pack_size(ctypes.byref(desc)))
-        pk = torch.empty(3, n, device=weight.device, dtype=torch.bfloat16)
-        _lib.check(_lib.load().eelg_linear_pack(_lib.ptr(weight), ctypes.byref(desc), _lib.ptr(pk),
-                                                _lib.stream(pk)), "linear_pack")
+        pk = pack_weights("linear_pack", desc, weight)
         self._pk_cache[which] = (key, pk)
         return pk
 
-    def _run_pk(self, which, x, x_row, weight, bias, extra, n, out, out_row, desc) -> bool:
-        """the packed launch when eligible; False leaves the call to the fp32 kernels"""
-        from . import _lib
-        if not (LIN_X6 and self._pk_ok[which] and x_row % 4 == 0 and out_row % 4 == 0
-                and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
-                and (extra is None or (extra.data_ptr() % 16 == 0 and desc.res_row == 0))):
-            return False
-        pk = self._packed(which, weight.detach())
-        _lib.check(_lib.load().eelg_linear_fwd_pk(
-            _lib.ptr(x), x_row, _lib.ptr(pk), _lib.ptr(bias), _lib.ptr(extra), n, _lib.ptr(out),
-            out_row, ctypes.byref(desc), _lib.stream(out)), "linear_fwd_pk")
-        return True
-
     # -- launches ---------------------------------------------------------------
     def _fwd(self, x, weight, bias, residual=None):
-        from . import _lib
         n = x.shape[0]
         y = torch.empty(n, self._out_dim, device=x.device, dtype=torch.float32)
         self._fwd_desc.max_rows = n * self._fwd_maxd
@@ -360,19 +400,14 @@ class _LinearKernels:
                                      or not residual.is_contiguous()):
             raise ValueError(f"residual {tuple(residual.shape)} {residual.dtype}: expected a "
                              f"contiguous float32 {want}")
-        if self._run_pk("fwd", x, self._in_dim, weight, bias, residual, n, y,
-                        self._out_dim, self._fwd_desc):
-            return y
-        _lib.check(_lib.load().eelg_linear_fwd_res(
-            _lib.ptr(x), self._in_dim, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(residual), n,
-            _lib.ptr(y), self._out_dim, ctypes.byref(self._fwd_desc), _lib.stream(y)),
-            "linear_fwd")
+        linear_apply("linear", "linear_fwd", self._fwd_desc, LIN_X6, x, self._in_dim, weight, bias,
+                     residual, n, y, self._out_dim, self._pk_ok["fwd"],
+                     lambda: self._packed("fwd", weight.detach()))
         return y
 
     def _bwd_x(self, gy, weight, extra=None, extra_pieces=None):
         """grad-x; ``extra`` (e.g. a residual's gradient) is added in the epilogue: rows of this
         linear's input layout, or compact rows of ``extra_pieces`` (its other slots add zero)"""
-        from . import _lib
         n = gy.shape[0]
         gx = torch.empty(n, self._in_dim, device=gy.device, dtype=torch.float32)
         desc, width = self._bx_desc, self._in_dim
@@ -384,37 +419,21 @@ class _LinearKernels:
             if tuple(extra.shape) != (n, width) or extra.dtype != torch.float32:
                 raise ValueError(f"linear grad-x: added gradient {tuple(extra.shape)} does not "
                                  f"match {(n, width)}")
-        if self._run_pk("bx", gy, self._out_dim, weight, None, extra, n, gx,
-                        self._in_dim, desc):
-            return gx
-        _lib.check(_lib.load().eelg_linear_fwd_res(
-            _lib.ptr(gy), self._out_dim, _lib.ptr(weight), None, _lib.ptr(extra), n,
-            _lib.ptr(gx), self._in_dim, ctypes.byref(desc), _lib.stream(gx)),
-            "linear_bwd_x")
+        linear_apply("linear", "linear_bwd_x", desc, LIN_X6, gy, self._out_dim, weight, None, extra,
+                     n, gx, self._in_dim, self._pk_ok["bx"],
+                     lambda: self._packed("bx", weight.detach()))
         return gx
 
     def _bwd_w(self, x, gy):
-        from . import _lib, ops
         n = x.shape[0]
         if not self._live_pairs:
             return torch.zeros(self.weight_numel, device=x.device, dtype=torch.float32)
-        # ~LINW_WG workgroups in total: (node slices) x (32x32 weight tiles of all
-        # instructions); each slice leaves one partial weight gradient that the sum reads back
-        slices = max(1, min((n + 31) // 32, -(-LINW_WG // self._bw_slice_tiles), LINW_MAX_SLICES))
-        nps = -(-n // slices)
-        slices = -(-n // nps)
         self._bw_desc.max_rows = n * self._bw_maxd
         # (a pruned linear writes the live weight entries only: the others sum exact zeros)
-        part = (torch.empty if self._bw_covers else torch.zeros)(
-            slices, self.weight_numel, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_linear_bwd_w(
-            _lib.ptr(x), self._in_dim, _lib.ptr(gy), self._out_dim, n, nps,
-            _lib.ptr(part), slices, self.weight_numel, ctypes.byref(self._bw_desc), _lib.stream(part)),
-            "linear_bwd_w")
-        return ops.sum_rows(part)
+        return linear_bwd_w("linear_bwd_w", self._bw_desc, x, self._in_dim, gy, self._out_dim, n,
+                            self._bw_slice_tiles, self.weight_numel, self._bw_covers)
 
     def _bwd_bias(self, gy):
-        from . import ops
         nb = sum(self.irreps_out[o].mul for o in self.bias_slots)
         live = [(self._b_offs[o] + b, off, cnt) for (o, b, cnt), off in zip(self._out_pieces, self._out_poff)
                 if o in self._b_offs]
@@ -510,13 +529,11 @@ class Linear(_LinearKernels, torch.nn.Module):
         kernel epilogue (the layer residual of ``gnn/model.py:92-96``).  ``grad_mailbox``
         shared by the residual-adding linear and the first linear reading the residual moves
         the residual's gradient into that linear's grad-x epilogue (``GradMailbox``)."""
-        from .ops import _f32, _require_device
-        _require_device(x)
+        ops._require_device(x)
         # live: the variant of set_live (compact rows of the live pieces) where one is set
         k = self.live if (live and self.live is not None) else self
         if x.shape[-1] != k._in_dim:
             raise ValueError(f"Linear expects [..., {k._in_dim}], got {tuple(x.shape)}")
-        from . import ops
         weight, bias = self.weight, self.bias
         side = None
         if ops.OVERLAP and x.is_cuda and torch.is_grad_enabled() and weight.requires_grad:
@@ -526,9 +543,9 @@ class Linear(_LinearKernels, torch.nn.Module):
                 if bias is not None:
                     bias = _OnStream.apply(bias, side)
         if residual is not None:
-            _require_device(residual)
-            residual = _f32(residual)
-        return _IrrepsLinearFn.apply(_f32(x), weight, bias, k, side, residual, grad_mailbox)
+            ops._require_device(residual)
+            residual = ops._f32(residual)
+        return _IrrepsLinearFn.apply(ops._f32(x), weight, bias, k, side, residual, grad_mailbox)
 
 
 class _GatePlan:
@@ -550,7 +567,6 @@ class _GatePlan:
         self._gdesc = None
 
     def desc(self):
-        from . import _lib
         if self._gdesc is None:
             d = _lib.GateDesc()
             d.n_scal, d.n_gates, d.n_blk = self.irreps_scalars.dim, self.n_gates, len(self.irreps_gated)
@@ -560,7 +576,6 @@ class _GatePlan:
         return self._gdesc
 
     def fits_kernel(self) -> bool:
-        from . import _lib
         return (len(self.irreps_gated) <= _lib.GATE_MAXBLK and self.irreps_gated.dim <= _lib.GATE_MAXGATED
                 and self.n_gates <= _lib.GATE_MAXGATES)
 
@@ -570,23 +585,20 @@ class _GateFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, plan: _GatePlan):
-        from . import _lib
         y = torch.empty(x.shape[0], plan.out_dim, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_gate_fwd(_lib.ptr(x), x.shape[0], ctypes.byref(plan.desc()),
-                                             float(plan.cst), _lib.ptr(y), _lib.stream(y)), "gate_fwd")
+        _lib.launch("gate_fwd", _lib.load().eelg_gate_fwd, x, x.shape[0], plan.desc(), float(plan.cst),
+                    y, on=y)
         ctx.save_for_backward(x)
         ctx.plan = plan
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        from . import _lib
         (x,) = ctx.saved_tensors
         gy = gy.contiguous()
         gx = torch.empty_like(x)
-        _lib.check(_lib.load().eelg_gate_bwd(_lib.ptr(x), _lib.ptr(gy), x.shape[0],
-                                             ctypes.byref(ctx.plan.desc()), float(ctx.plan.cst),
-                                             _lib.ptr(gx), _lib.stream(gx)), "gate_bwd")
+        _lib.launch("gate_bwd", _lib.load().eelg_gate_bwd, x, gy, x.shape[0], ctx.plan.desc(),
+                    float(ctx.plan.cst), gx, on=gx)
         return gx, None
 
 
@@ -641,8 +653,7 @@ class Gate(torch.nn.Module):
         # the fused HIP passes cover gates up to the kernels' table sizes; wider readouts use
         # the torch form below (the readout tail is outside the HIP hot path)
         if x.is_cuda and x.dtype == torch.float32 and GATE_FUSED and plan.fits_kernel():
-            from .ops import _f32
-            return _GateFn.apply(_f32(x), plan)
+            return _GateFn.apply(ops._f32(x), plan)
         # one torch.split instead of per-block slices: its backward is a single cat, where
         # slice backwards would each zero-fill a full [n, dim_in] gradient and add it up
         # (six zero-fill + add pairs per gate; the values are identical either way)

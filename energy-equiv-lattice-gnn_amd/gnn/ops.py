@@ -18,51 +18,8 @@ import torch
 from . import _lib
 
 
-class KernelTimer:
-    """Optional HIP-event timing of selected launches (used by ``bench.py``).
-
-    Events are recorded on the current stream, the one every op launches on."""
-
-    def __init__(self):
-        self.enabled = False
-        self.records: Dict[str, list] = {}
-
-    def start(self, name: str):
-        if not self.enabled:
-            return None
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        return (name, ev)
-
-    def stop(self, tok) -> None:
-        if tok is None:
-            return
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        self.records.setdefault(tok[0], []).append((tok[1], ev))
-
-    def summary(self) -> Dict[str, Dict[str, float]]:
-        torch.cuda.synchronize()
-        out = {}
-        for name, pairs in self.records.items():
-            ms = [a.elapsed_time(b) for a, b in pairs]
-            out[name] = {"count": len(ms), "mean_ms": sum(ms) / len(ms), "total_ms": sum(ms)}
-        return out
-
-
-TIMER = KernelTimer()
-
-
-def _launch(name: str, fn, *args, on: torch.Tensor, timed: Optional[str] = None) -> None:
-    """``fn(*args, stream)`` on the current stream of ``on``'s device, checked under the error
-    label ``name``; ``timed``: the ``TIMER`` label of the launch.  Tensors and None pass as
-    addresses, ctypes structures by reference, numbers and raw addresses as they are; dtype,
-    layout and alignment are the caller's."""
-    argv = [a.data_ptr() if isinstance(a, torch.Tensor)
-            else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args]
-    tok = TIMER.start(timed) if timed is not None else None
-    _lib.check(fn(*argv, _lib.stream(on)), name)
-    TIMER.stop(tok)
+# the one launch path and its timer live in the leaf module; these names stay for callers
+KernelTimer, TIMER, _launch = _lib.KernelTimer, _lib.TIMER, _lib.launch
 
 # side-stream overlap of independent work (radial MLPs, symmetric-contraction coefficient
 # chain and its gradient); EELG_OVERLAP=0 runs everything in line on the current stream
@@ -284,11 +241,9 @@ def _edge_embed_fwd(pos, csr: EdgeCSR, shifts_sorted, radius_sorted, lmax: int, 
     nsh = (lmax + 1) ** 2
     sh = torch.empty(e, sh_row_stride(nsh), device=pos.device, dtype=torch.float32)
     feats = torch.empty(e, 2 * nb, device=pos.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.eelg_edge_embed(
-        _lib.ptr(_f32(pos)), _lib.ptr(csr.sender), _lib.ptr(csr.receiver),
-        _lib.ptr(_f32(shifts_sorted)), _lib.ptr(_f32(radius_sorted)), e, lmax, nb,
-        float(len_end), float(rad_end), _lib.ptr(sh), _lib.ptr(feats), _lib.stream(sh)), "edge_embed")
+    _launch("edge_embed", _lib.load().eelg_edge_embed, _f32(pos), csr.sender, csr.receiver,
+            _f32(shifts_sorted), _f32(radius_sorted), e, lmax, nb, float(len_end), float(rad_end),
+            sh, feats, on=sh)
     return sh[:, :nsh], feats          # [E, nsh] view of the padded rows the TP kernels read
 
 
@@ -399,8 +354,8 @@ def segment_sum_csr(src, rowptr, n_rows: int, idx=None, row_scale=None, scale: f
     out = torch.empty((n_rows,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
     lib = _lib.load()
     fn = lib.eelg_segment_sum_csr_bf16 if bf else lib.eelg_segment_sum_csr
-    _lib.check(fn(_lib.ptr(src), _lib.ptr(rowptr), _lib.ptr(idx), _lib.ptr(row_scale), float(scale),
-                  n_rows, int(width), _lib.ptr(out), _lib.stream(out)), "segment_sum_csr")
+    _launch("segment_sum_csr", fn, src, rowptr, idx, row_scale, float(scale), n_rows, int(width), out,
+            on=out)
     return out
 
 
@@ -471,9 +426,8 @@ class _SegmentOrder(torch.autograd.Function):
         out = torch.empty(n_rows, width, device=src.device, dtype=torch.float32)
         arg = (torch.empty(n_rows, width, device=src.device, dtype=torch.int32)
                if op != _ORDER_OPS["mul"] else None)
-        _lib.check(_lib.load().eelg_segment_order(_lib.ptr(src), _lib.ptr(rowptr), n_rows, width,
-                                                  op, _lib.ptr(out), _lib.ptr(arg),
-                                                  _lib.stream(out)), "segment_order")
+        _launch("segment_order", _lib.load().eelg_segment_order, src, rowptr, n_rows, width, op, out,
+                arg, on=out)
         ctx.save_for_backward(src, rowptr, arg)
         ctx.n_rows, ctx.op, ctx.covered = n_rows, op, covered
         return out
@@ -484,9 +438,8 @@ class _SegmentOrder(torch.autograd.Function):
         g = _f32(g)
         # every row of every segment is written; rows outside all segments must read 0
         gs = torch.empty_like(src) if ctx.covered else torch.zeros_like(src)
-        _lib.check(_lib.load().eelg_segment_order_bwd(
-            _lib.ptr(src), _lib.ptr(rowptr), _lib.ptr(arg), _lib.ptr(g), ctx.n_rows, src.shape[1],
-            ctx.op, _lib.ptr(gs), _lib.stream(gs)), "segment_order_bwd")
+        _launch("segment_order_bwd", _lib.load().eelg_segment_order_bwd, src, rowptr, arg, g,
+                ctx.n_rows, src.shape[1], ctx.op, gs, on=gs)
         return gs, None, None, None, None
 
 
@@ -623,9 +576,8 @@ def _segment_pna_composed(src, rowptr32, n_rows: int, weight, scalers, args):
         for op in ("min", "max"):
             kept[op] = torch.empty(n_rows, src.shape[1], device=src.device, dtype=torch.int32)
             val = torch.empty(n_rows, src.shape[1], device=src.device, dtype=torch.float32)
-            _lib.check(_lib.load().eelg_segment_order(
-                _lib.ptr(src.detach()), _lib.ptr(rowptr32), n_rows, src.shape[1], _ORDER_OPS[op],
-                _lib.ptr(val), _lib.ptr(kept[op]), _lib.stream(val)), "segment_order")
+            _launch("segment_order", _lib.load().eelg_segment_order, src.detach(), rowptr32, n_rows,
+                    src.shape[1], _ORDER_OPS[op], val, kept[op], on=val)
         args.argmin, args.argmax = kept["min"], kept["max"]
     stack = torch.stack([a * scalers[:, None, s] for a in (mean, mn, mx, std) for s in range(3)], 2)
     return (stack * weight.reshape(12)).sum(-1)
@@ -1195,9 +1147,8 @@ class _SymConTable(torch.autograd.Function):
                              f"{tab.mul}, D {tab.D}, ldc {tab.ldc}")
         terms, _ = tab.on(x.device)
         out = torch.empty(n, tab.mul * tab.Dout, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().eelg_scg_fwd(ctypes.byref(tab.desc), _lib.ptr(terms), _lib.ptr(x), x.shape[1],
-                                            _lib.ptr(coef), tab.ldc, n, _lib.ptr(out), out.shape[1],
-                                            _lib.stream(out)), "scg_fwd")
+        _launch("scg_fwd", _lib.load().eelg_scg_fwd, tab.desc, terms, x, x.shape[1], coef, tab.ldc, n,
+                out, out.shape[1], on=out)
         ctx.save_for_backward(x, coef)
         ctx.tab = tab
         return out
@@ -1213,15 +1164,13 @@ class _SymConTable(torch.autograd.Function):
         gx = gcoef = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            _lib.check(lib.eelg_scg_bwd_x(ctypes.byref(tab.desc), _lib.ptr(terms), _lib.ptr(x), x.shape[1],
-                                          _lib.ptr(coef), tab.ldc, _lib.ptr(g), g.shape[1], n, _lib.ptr(gx),
-                                          _lib.stream(gx)), "scg_bwd_x")
+            _launch("scg_bwd_x", lib.eelg_scg_bwd_x, tab.desc, terms, x, x.shape[1], coef, tab.ldc, g,
+                    g.shape[1], n, gx, on=gx)
         if ctx.needs_input_grad[1]:
             nch = max(1, -(-n // _lib.SCG_CHUNK))
             part = torch.zeros(nch, tab.mul, tab.ldc, device=x.device, dtype=torch.float32)
-            _lib.check(lib.eelg_scg_bwd_coef(ctypes.byref(tab.desc), _lib.ptr(terms), _lib.ptr(outs), tab.ldc,
-                                             _lib.ptr(x), x.shape[1], _lib.ptr(g), g.shape[1], n,
-                                             _lib.ptr(part), _lib.stream(part)), "scg_bwd_coef")
+            _launch("scg_bwd_coef", lib.eelg_scg_bwd_coef, tab.desc, terms, outs, tab.ldc, x,
+                    x.shape[1], g, g.shape[1], n, part, on=part)
             gcoef = sum_rows(part)
         return gx, gcoef, None
 
@@ -1261,8 +1210,7 @@ def split_bf16x3(t: torch.Tensor) -> torch.Tensor:
     _require_device(t)
     t = _f32(t)
     parts = torch.empty((3,) + tuple(t.shape), device=t.device, dtype=torch.bfloat16)
-    _lib.check(_lib.load().eelg_split_bf16x3(_lib.ptr(t), t.numel(), _lib.ptr(parts),
-                                             _lib.stream(parts)), "split_bf16x3")
+    _launch("split_bf16x3", _lib.load().eelg_split_bf16x3, t, t.numel(), parts, on=parts)
     return parts
 
 
@@ -1286,8 +1234,8 @@ def sum_rows(part: torch.Tensor, out: torch.Tensor = None, scale: float = 1.0) -
     lib = _lib.load()
     nw = lib.eelg_sum_rows_work(rows, cols)
     work = torch.empty(nw, device=part.device, dtype=torch.float32) if nw else None
-    _lib.check(lib.eelg_sum_rows(_lib.ptr(part), max(ld, cols), rows, cols, float(scale), _lib.ptr(out),
-                                 _lib.ptr(work), nw, _lib.stream(out)), "sum_rows")
+    _launch("sum_rows", lib.eelg_sum_rows, part, max(ld, cols), rows, cols, float(scale), out, work, nw,
+            on=out)
     return out
 
 
@@ -1597,9 +1545,8 @@ class SparseRows:
 
 def _spmm(trip, n_rows, B, ldb_r, ldb_c, n_cols, out, ldo_r, ldo_c):
     rp, col, val = trip
-    _lib.check(_lib.load().eelg_csr_spmm(_lib.ptr(rp), _lib.ptr(col), _lib.ptr(val), n_rows,
-                                         _lib.ptr(B), ldb_r, ldb_c, n_cols, _lib.ptr(out), ldo_r,
-                                         ldo_c, _lib.stream(out)), "csr_spmm")
+    _launch("csr_spmm", _lib.load().eelg_csr_spmm, rp, col, val, n_rows, B, ldb_r, ldb_c, n_cols, out,
+            ldo_r, ldo_c, on=out)
 
 
 class _SymConCoef(torch.autograd.Function):

@@ -219,14 +219,13 @@ class FlatAdamW(torch.optim.Optimizer):
         if self.fused:
             lib = _lib.load()
             with torch.cuda.device(self.flat_p.device):
-                stream = _lib.stream(self.flat_p)
-                _lib.check(lib.eelg_grad_sqnorm(_lib.ptr(self.flat_g), self.numel, _lib.ptr(self._partials),
-                                                stream), "grad_sqnorm")
-                _lib.check(lib.eelg_adamw_flat(
-                    _lib.ptr(self.flat_p), _lib.ptr(self.flat_m), _lib.ptr(self.flat_v), _lib.ptr(self.flat_vmax),
-                    _lib.ptr(self.flat_g), self.numel, _lib.ptr(self._partials), float(g["lr"]),
-                    float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                    self.max_norm, int(g["amsgrad"]), _lib.ptr(src), _lib.ptr(dst), stream), "adamw_flat")
+                _lib.launch("grad_sqnorm", lib.eelg_grad_sqnorm, self.flat_g, self.numel, self._partials,
+                            on=self.flat_p)
+                _lib.launch("adamw_flat", lib.eelg_adamw_flat, self.flat_p, self.flat_m, self.flat_v,
+                            self.flat_vmax, self.flat_g, self.numel, self._partials, float(g["lr"]),
+                            float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                            float(g["weight_decay"]), self.max_norm, int(g["amsgrad"]), src, dst,
+                            on=self.flat_p)
         else:
             self._step_composed(g, src, dst)
         self._calls += 1

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""Ledger of the host launch paths in ``gnn/ops.py``: fixed-seed forward / backward passes through
-every branch the autograd wrappers take, each recorded as the sha256 of every output and gradient
-(raw bytes on the host) and the ``ops.TIMER`` name -> count map of the pass.  Two trees that run
-the same kernels with the same operands in the same order write equal ledgers:
+"""Ledger of the host launch paths in ``gnn/``: fixed-seed forward / backward passes through
+every branch the autograd wrappers, the linears, the gate and the optimizer take, each recorded
+as the sha256 of every output and gradient (raw bytes on the host), the ``ops.TIMER`` name ->
+count map of the pass and the ordered error labels handed to ``_lib.check`` (one per launch).
+Two trees that run the same kernels with the same operands in the same order write equal ledgers:
 
     python tools/op_ledger.py --out ledger.json        # run in each tree, compare the files
     python tools/op_ledger.py --compare a.json b.json  # lists the entries that differ
@@ -27,7 +28,8 @@ def compare(a_path: str, b_path: str) -> int:
         ha, hb = a.get(k, {}).get("sha256", {}), b.get(k, {}).get("sha256", {})
         diff = sorted(n for n in set(ha) | set(hb) if ha.get(n) != hb.get(n))
         print(f"DIFF {k}: tensors {diff}; launches equal: "
-              f"{a.get(k, {}).get('launches') == b.get(k, {}).get('launches')}")
+              f"{a.get(k, {}).get('launches') == b.get(k, {}).get('launches')}; labels equal: "
+              f"{a.get(k, {}).get('labels') == b.get(k, {}).get('labels')}")
     print(f"{len(a)} / {len(b)} cases, {len(bad)} differ")
     return 1 if bad else 0
 
@@ -41,12 +43,19 @@ def main() -> int:
         return compare(*args.compare)
 
     import torch
-    from gnn import EnergyEquivGNN, SyntheticLattices, _lib, collate, ops, torch_ops  # noqa: F401
+    from gnn import EnergyEquivGNN, SyntheticLattices, _lib, collate, dense, o3, ops, torch_ops  # noqa: F401
     from gnn.mace import SymmetricContraction
+    from gnn.optim import FlatAdamW
     from gnn.train import stiffness_loss
 
-    ledger, models = {}, {}
+    ledger, models, labels = {}, {}, []
     ops.TIMER.enabled = True
+    real_check = _lib.check
+
+    def check(rc, what):                                    # every launch passes its label here
+        labels.append(what)
+        return real_check(rc, what)
+    _lib.check = check
 
     def rand(*shape, seed, grad=False, dtype=torch.float32):
         t = torch.randn(*shape, generator=torch.Generator().manual_seed(seed)).to(DEV).to(dtype)
@@ -58,6 +67,7 @@ def main() -> int:
         for k, v in switches.items():
             setattr(ops, k, v)
         ops.TIMER.records = {}
+        del labels[:]
         try:
             tensors = fn()
             torch.cuda.synchronize()
@@ -66,7 +76,8 @@ def main() -> int:
                 setattr(ops, k, v)
         sha = {k: hashlib.sha256(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
                for k, t in tensors.items() if t is not None}
-        ledger[name] = {"sha256": sha, "launches": {k: len(v) for k, v in sorted(ops.TIMER.records.items())}}
+        ledger[name] = {"sha256": sha, "launches": {k: len(v) for k, v in sorted(ops.TIMER.records.items())},
+                        "labels": list(labels)}
 
     ds = SyntheticLattices(2, 24, 96, seed=7)
 
@@ -175,6 +186,131 @@ def main() -> int:
         record(f"e/torch_ops.tp_interaction/bf16={bf}", lambda: custom_tp(bf))
     for want in ((True, False), (False, True), (True, True)):
         record(f"e/symmetric_contraction/x{int(want[0])}coef{int(want[1])}", lambda: symcon(*want))
+
+    H3, WIDE, NARROW = "32x0e+32x1o+32x2e", "160x0e+160x1o", "32x0e+32x1o"
+
+    def o3_linear(irr_in, irr_out, biases=False, residual=False, live_out=None):    # (f) o3.Linear
+        torch.manual_seed(11)
+        lin = o3.Linear(irr_in, irr_out, biases=biases).to(DEV)
+        if live_out is not None:
+            lin.set_live(None, live_out)
+        x = rand(33, lin.irreps_in.dim, seed=12, grad=True)
+        r = rand(33, lin.irreps_out.dim, seed=13, grad=True) if residual else None
+        y = lin(x, residual=r, live=live_out is not None)
+        y.backward(rand(*y.shape, seed=14))
+        return grads(lin, {"y": y, "grad.x": x.grad, "grad.residual": None if r is None else r.grad})
+
+    def o3_mailbox():                                       # the layer residual through two linears
+        torch.manual_seed(15)
+        up, down = o3.Linear(NARROW, WIDE).to(DEV), o3.Linear(WIDE, NARROW, biases=True).to(DEV)
+        h, mb = rand(33, 128, seed=16, grad=True), o3.GradMailbox()
+        y = down(up(h, grad_mailbox=mb), residual=h, grad_mailbox=mb)
+        y.backward(rand(*y.shape, seed=17))
+        out = {"y": y, "grad.h": h.grad}
+        out.update({"up." + k: v for k, v in grads(up, {}).items()})
+        out.update({"down." + k: v for k, v in grads(down, {}).items()})
+        return out
+
+    for biases in (False, True):
+        record(f"f/o3.Linear/k32/biases{int(biases)}", lambda: o3_linear(H3, H3, biases))
+    record("f/o3.Linear/k160", lambda: o3_linear(WIDE, NARROW, True))
+    record("f/o3.Linear/k160/residual", lambda: o3_linear(WIDE, NARROW, True, residual=True))
+    record("f/o3.Linear/k160/mailbox", o3_mailbox)
+    record("f/o3.Linear/k32/live_out", lambda: o3_linear(H3, H3, True, True, ((0, 0, 32), (2, 0, 32))))
+
+    def dense_linear(cls, k, n_out, n):                     # (g) dense.Linear / SmallInLinear
+        torch.manual_seed(21)
+        lin = cls(k, n_out).to(DEV)
+        x = rand(n, k, seed=22, grad=cls is dense.Linear)
+        y = lin(x)
+        y.backward(rand(*y.shape, seed=23))
+        return grads(lin, {"y": y, "grad.x": x.grad})
+
+    for k, n_out, n in ((128, 64, 33), (128, 64, 4097), (128, 128, 33), (48, 40, 33)):
+        record(f"g/dense.Linear/{k}to{n_out}/n{n}", lambda: dense_linear(dense.Linear, k, n_out, n))
+    record("g/dense.SmallInLinear/3to32/n33", lambda: dense_linear(dense.SmallInLinear, 3, 32, 33))
+
+    def gate(live):                                         # (h) the readout Gate
+        g = o3.Gate("16x0e", "16x0e", "8x1o+8x2e")
+        if live:
+            g.set_live(gated=(0,))
+        x = rand(5, g.live.in_dim if live else g.irreps_in.dim, seed=31, grad=True)
+        y = g(x, live=live)
+        y.backward(rand(*y.shape, seed=32))
+        return {"y": y, "grad.x": x.grad}
+
+    for live in (False, True):
+        record(f"h/Gate/live{int(live)}", lambda: gate(live))
+
+    rowptr = torch.tensor([0, 3, 3, 8, 9, 14, 15, 20], dtype=torch.int32).to(DEV)   # (i) ops.py
+    perm = torch.randperm(20, generator=torch.Generator().manual_seed(41)).to(torch.int32).to(DEV)
+
+    def seg_sum(width, dtype, idx):
+        return {"out": ops.segment_sum_csr(rand(20, width, seed=42, dtype=dtype), rowptr, 7, idx=idx)}
+
+    def seg_order(reduce):
+        src = rand(20, 6, seed=43, grad=True)
+        out = ops.segment_order(src, rowptr, 7, reduce)
+        out.backward(rand(7, 6, seed=44))
+        return {"out": out, "grad.src": src.grad}
+
+    def symcon_table():
+        torch.manual_seed(45)
+        hid = "16x0e+16x1o+16x2e"
+        sc = SymmetricContraction(hid, hid, 4).to(DEV)
+        x, coef = rand(33, 16 * 9, seed=46, grad=True), sc.coefficients().detach().requires_grad_(True)
+        y = ops.symmetric_contraction_table(x, coef, sc._table)
+        y.backward(rand(*y.shape, seed=47))
+        return {"y": y, "grad.x": x.grad, "grad.coef": coef.grad}
+
+    def symcon_coef():
+        torch.manual_seed(48)
+        sc = SymmetricContraction(HID4, HID4, 3).to(DEV)
+        coef = sc.coefficients()
+        coef.backward(rand(*coef.shape, seed=49))
+        return grads(sc, {"coef": coef})
+
+    def sum_rows():
+        wide, out = rand(9, 20, seed=51), torch.zeros(7, device=DEV)
+        ops.sum_rows(wide[:, 11:18], out=out, scale=0.5)
+        return {"contiguous3d": ops.sum_rows(rand(5, 3, 7, seed=50)), "strided": ops.sum_rows(wide[:, 4:11]),
+                "out": out}
+
+    def embed(geometry):
+        b = collate([ds[0], ds[1]]).to(DEV)
+        csr = EnergyEquivGNN.edge_graph(b)
+        b.positions.requires_grad_(geometry)
+        sh, feats = ops.edge_embed(b.positions, csr, b.shifts[csr.perm], b.edge_attr[csr.perm].reshape(-1),
+                                   4, 6, 0.6, ds.max_edge_radius)
+        if geometry:
+            ((sh * rand(*sh.shape, seed=52)).sum() + (feats * rand(*feats.shape, seed=53)).sum()).backward()
+        return {"sh": sh, "feats": feats, "grad.positions": b.positions.grad}
+
+    for width in (6, 260):
+        for tag, dtype, idx in (("fp32", torch.float32, None), ("bf16", torch.bfloat16, None),
+                                ("idx", torch.float32, perm)):
+            record(f"i/segment_sum_csr/{width}/{tag}", lambda: seg_sum(width, dtype, idx))
+    for reduce in ("max", "min", "mul"):
+        record(f"i/segment_order/{reduce}", lambda: seg_order(reduce))
+    record("i/symmetric_contraction_table", symcon_table)
+    record("i/split_bf16x3", lambda: {"parts": ops.split_bf16x3(rand(33, 7, seed=54))})
+    record("i/sum_rows", sum_rows)
+    record("i/symcon_coefficients", symcon_coef)
+    for geometry in (False, True):
+        record(f"i/edge_embed/geometry{int(geometry)}", lambda: embed(geometry))
+
+    def adamw():                                            # (j) two fused optimizer steps
+        ps = [torch.nn.Parameter(rand(*shape, seed=60 + i)) for i, shape in enumerate(((5, 3), (8,), (4, 4)))]
+        opt = FlatAdamW(ps, lr=1e-2, max_norm=1.0)
+        for it in range(2):
+            for i, p in enumerate(ps):
+                p.grad = rand(*p.shape, seed=70 + 3 * it + i)
+            opt.step()
+        out = {f"p{i}": p for i, p in enumerate(ps)}
+        out.update(m=opt.flat_m, v=opt.flat_v, state=opt._row())
+        return out
+
+    record("j/FlatAdamW", adamw)
 
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
