@@ -233,20 +233,15 @@ EELG_HD inline void eelg_elastic_abc_spread(double* p, const double* abc) {
 }
 
 // g_C [36] = -S G_S S + the direct terms, both triangles written from one packed result (exactly
-// symmetric).  s32: the compliance as the forward stored it ([36] fp32, lower triangle read).
-// gsm [21]: the directional part sum_p w_p m m^T of G_S (the a, b, c part is added here; gsm is
-// used up).  spd == 0: the direct terms alone, S and gsm are not read.
-EELG_HD inline void eelg_elastic_grad_c(const float* s32, double* gsm, const double* gs, const double* gc,
-                                        int spd, float* out) {
+// symmetric).  s [21]: the compliance, packed fp64.  gsm [21]: the directional part of G_S (the a, b,
+// c part is added here; gsm is used up).  spd == 0: the direct terms alone, s and gsm are not read.
+EELG_HD inline void eelg_elastic_grad_c_packed(const double* s, double* gsm, const double* gs, const double* gc,
+                                               int spd, float* out) {
   double r[21];
 #pragma unroll
   for (int i = 0; i < 21; ++i) r[i] = 0.0;
   if (spd) {
-    double s[21], t[36];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = 0; j <= i; ++j) s[eelg_el_tri(i, j)] = s32[6 * i + j];
+    double t[36];
     eelg_elastic_abc_spread(gsm, gs);
 #pragma unroll
     for (int i = 0; i < 6; ++i)
@@ -272,6 +267,22 @@ EELG_HD inline void eelg_elastic_grad_c(const float* s32, double* gsm, const dou
   for (int i = 0; i < 6; ++i)
 #pragma unroll
     for (int j = 0; j < 6; ++j) out[6 * i + j] = (float)r[eelg_el_tri(i, j)];
+}
+
+// The same from the compliance as the forward of csrc/eelg_elastic.hip stored it: s32 [36] fp32,
+// lower triangle read (not read with spd == 0).  gsm: sum_p w_p m m^T.
+EELG_HD inline void eelg_elastic_grad_c(const float* s32, double* gsm, const double* gs, const double* gc,
+                                        int spd, float* out) {
+  double s[21];
+#pragma unroll
+  for (int i = 0; i < 21; ++i) s[i] = 0.0;
+  if (spd) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) s[eelg_el_tri(i, j)] = s32[6 * i + j];
+  }
+  eelg_elastic_grad_c_packed(s, gsm, gs, gc, spd, out);
 }
 
 #endif  // EELG_ELASTIC_H

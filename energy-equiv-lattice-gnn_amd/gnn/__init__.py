@@ -17,6 +17,8 @@ from .device_data import DeviceDataset, DeviceLoader, pack_graphs  # noqa: F401
 from .metrics import (METRIC_COLUMNS, ErrorTable, aggr_errors, evaluate, metric_directions,  # noqa: F401
                       obtain_errors, stiffness_metrics, validation_metrics)
 from .elastic import ELASTIC_COLUMNS, elastic_properties, elastic_properties_composed  # noqa: F401
+from .transverse import (TRANSVERSE_COLUMNS, TRANSVERSE_DIR_COLUMNS, transverse_properties,  # noqa: F401
+                         transverse_properties_composed)
 from .optim import FlatAdamW  # noqa: F401
 from .trainer import Callback, EarlyStopping, ModelCheckpoint, Trainer  # noqa: F401
 

@@ -109,6 +109,9 @@ _SIGS = {
     # elastic properties of predicted stiffness matrices and their gradient
     "eelg_elastic_props": ([_P, _P, _I, _I, _P, _P, _P, _P], _I),
     "eelg_elastic_props_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
+    # shear, Poisson's ratio and compressibility surfaces and their gradient
+    "eelg_transverse_props": ([_P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    "eelg_transverse_props_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
     # the tail of the training step: loss + gradient, gradient norm partials, clip + AdamW
     "eelg_stiffness_loss": ([_P, _P, _I, _I, _F, _P, _P, _P], _I),
     "eelg_sqnorm_parts": ([_LL], _I),
@@ -148,7 +151,9 @@ class LinWDesc(ctypes.Structure):
 BATCH_MAXW = 64          # include/eelg.h EELG_BATCH_MAXW
 METRICS_COLS = 16        # include/eelg.h EELG_METRICS_COLS
 ELASTIC_COLS = 12        # include/eelg.h EELG_ELASTIC_COLS
-OPTIM_STATE_COLS = 4     # include/eelg.h EELG_OPTIM_STATE_COLS
+TRANSVERSE_COLS = 7      # include/eelg.h EELG_TRANSVERSE_COLS
+TRANSVERSE_DIR_COLS = 5  # include/eelg.h EELG_TRANSVERSE_DIR_COLS
+OPTIM_STATE_COLS = 4    # include/eelg.h EELG_OPTIM_STATE_COLS
 DESIGN_THREADS = 256     # include/eelg.h EELG_DESIGN_THREADS
 
 

@@ -5,7 +5,8 @@ The gradients run on the HIP backward path of the model (``eelg_tp_bwd_sh``,
 ``eelg_radial_bwd_x``, ``eelg_edge_embed_bwd`` and the kernels the training backward uses);
 they are deterministic (no atomics) and fp32.  Second derivatives are not built.
 ``property_sensitivity`` starts the same backward from the elastic properties of the stiffness
-(``gnn.elastic``: moduli, Poisson's ratio, anisotropy, directional Young's modulus).
+(``gnn.elastic``: moduli, Poisson's ratio, anisotropy, directional Young's modulus; ``gnn.transverse``:
+the shear, Poisson's ratio and compressibility surfaces).
 
 ``optimize_design`` closes the loop: it changes strut radii and node positions down those gradients
 at constant strut volume.  The tail of an iteration -- tie the two directions of every strut, check
@@ -58,7 +59,9 @@ def stiffness_sensitivity(model, batch, cotangent: Optional[torch.Tensor] = None
 
 
 def property_sensitivity(model, batch, weights: torch.Tensor, directions: Optional[torch.Tensor] = None,
-                         dir_weights: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                         dir_weights: Optional[torch.Tensor] = None, *,
+                         transverse_weights: Optional[torch.Tensor] = None,
+                         transverse_dir_weights: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """``{'stiffness', 'properties', 'e_dir', 'positions', 'edge_attr', 'shifts'}``: the model's
     stiffness [B, 6, 6], its elastic properties [B, 12] (``gnn.elastic.ELASTIC_COLUMNS``) and
     directional Young's moduli [B, P] over ``directions`` [P, 3] (all detached), and the gradients of
@@ -71,16 +74,31 @@ def property_sensitivity(model, batch, weights: torch.Tensor, directions: Option
     None.  One model forward, one backward, no host synchronisation.  A graph whose predicted
     stiffness is not positive definite contributes the gradient of its ``K_V`` / ``G_V`` terms
     alone.  Frozen parameters, the untouched ``batch`` and thread safety: as
-    ``stiffness_sensitivity``."""
-    return _geometry_gradients(model, batch, _property_cotangents(weights, directions, dir_weights))
+    ``stiffness_sensitivity``.
+
+    ``transverse_weights`` [B, 7] (``gnn.transverse.TRANSVERSE_COLUMNS``; its ``spd`` column as
+    above) and ``transverse_dir_weights`` [B, P, 5] (``TRANSVERSE_DIR_COLUMNS``) over the same
+    ``directions`` add ``sum(transverse_weights * transverse) + sum(transverse_dir_weights * t_dir)``
+    to the objective: "how does the most negative Poisson's ratio change if I thicken this strut".
+    With either of them the result gains ``'transverse'`` [B, 7] and ``'t_dir'`` [B, P, 5] (detached)
+    and the call two more launches; a graph that is not positive definite contributes nothing through
+    them.  With both ``None`` nothing changes."""
+    return _geometry_gradients(model, batch, _property_cotangents(
+        weights, directions, dir_weights, transverse_weights=transverse_weights,
+        transverse_dir_weights=transverse_dir_weights))
 
 
-def _property_cotangents(weights, directions, dir_weights, who: str = "property_sensitivity"):
-    """The ``cotangents`` function of ``sum(weights * properties) + sum(dir_weights * e_dir)``."""
+def _property_cotangents(weights, directions, dir_weights, who: str = "property_sensitivity", *,
+                         transverse_weights=None, transverse_dir_weights=None):
+    """The ``cotangents`` function of ``sum(weights * properties) + sum(dir_weights * e_dir)`` plus,
+    where given, the same two sums over the transverse rows."""
     from .elastic import ELASTIC_COLUMNS, elastic_properties
     n_dirs = 0 if directions is None else int(directions.shape[0])
     if dir_weights is not None and directions is None:
         raise ValueError(f"{who}: dir_weights without directions")
+    transverse = transverse_weights is not None or transverse_dir_weights is not None
+    if transverse and directions is None:
+        raise ValueError(f"{who}: transverse_weights / transverse_dir_weights without directions")
 
     def cotangents(c):
         nb = int(c.shape[0])
@@ -95,7 +113,21 @@ def _property_cotangents(weights, directions, dir_weights, who: str = "property_
         if dir_weights is not None:
             outputs.append(e_dir)
             grads.append(dir_weights.to(device=e_dir.device, dtype=e_dir.dtype))
-        return {"properties": props.detach(), "e_dir": e_dir.detach()}, outputs, grads
+        extra = {"properties": props.detach(), "e_dir": e_dir.detach()}
+        if transverse:
+            from .transverse import TRANSVERSE_COLUMNS, TRANSVERSE_DIR_COLUMNS, transverse_properties
+            for name, w, shape in (("transverse_weights", transverse_weights, (nb, len(TRANSVERSE_COLUMNS))),
+                                   ("transverse_dir_weights", transverse_dir_weights,
+                                    (nb, n_dirs, len(TRANSVERSE_DIR_COLUMNS)))):
+                if w is not None and tuple(w.shape) != shape:
+                    raise ValueError(f"{who}: {name} {tuple(w.shape)}, expected {list(shape)}")
+            t_props, t_dir, _, _ = transverse_properties(c, directions.to(c.device))
+            for out, w in ((t_props, transverse_weights), (t_dir, transverse_dir_weights)):
+                if w is not None:
+                    outputs.append(out)
+                    grads.append(w.to(device=out.device, dtype=out.dtype))
+            extra.update(transverse=t_props.detach(), t_dir=t_dir.detach())
+        return extra, outputs, grads
     return cotangents
 
 
@@ -384,8 +416,9 @@ def design_step(layout: DesignLayout, g_pos, g_r, pos, r, pos0, m_pos, m_r, shif
 
 
 def optimize_design(model, batch, *, target: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
-                    directions: Optional[torch.Tensor] = None, dir_weights: Optional[torch.Tensor] = None, steps: int,
-                    step_r: float = 0.0, step_pos: float = 0.0, beta: float = 0.0, r_min: float,
+                    directions: Optional[torch.Tensor] = None, dir_weights: Optional[torch.Tensor] = None,
+                    transverse_weights: Optional[torch.Tensor] = None,
+                    transverse_dir_weights: Optional[torch.Tensor] = None, steps: int, step_r: float = 0.0, step_pos: float = 0.0, beta: float = 0.0, r_min: float,
                     r_max: Optional[float] = None, move_limit: float, keep_volume: bool = True) -> DesignResult:
     """Change the strut radii and node positions of every lattice of ``batch`` to lower an
     objective of its predicted stiffness ``C``, ``steps`` iterations of ``design_step`` at constant
@@ -395,7 +428,10 @@ def optimize_design(model, batch, *, target: Optional[torch.Tensor] = None, weig
     * ``weights`` [B, 12] and / or ``dir_weights`` [B, P] over ``directions`` [P, 3]:
       ``J = sum(weights * properties) + sum(dir_weights * e_dir)`` with the meaning they have in
       ``property_sensitivity`` (a zero weight skips its column, NaN or not); negative weights
-      maximise.
+      maximise.  ``transverse_weights`` [B, 7] and / or ``transverse_dir_weights`` [B, P, 5] add
+      ``sum(transverse_weights * transverse) + sum(transverse_dir_weights * t_dir)`` likewise: a
+      negative weight on ``nu_min`` asks for a more auxetic lattice, a negative weight on ``G_min``
+      stiffens the softest shear.
 
     ``step_r`` / ``step_pos``: the largest change of a radius / a position component per iteration
     from rest (0: that group stays); ``beta``: heavy-ball momentum; radii stay in ``[r_min, r_max]``
@@ -413,11 +449,12 @@ def optimize_design(model, batch, *, target: Optional[torch.Tensor] = None, weig
     from .model import EnergyEquivGNN, storage_dtype
     who = "optimize_design"
     nb = int(batch.num_graphs)
-    linear = weights is not None or dir_weights is not None
+    transverse = transverse_weights is not None or transverse_dir_weights is not None
+    linear = weights is not None or dir_weights is not None or transverse
     if target is not None and linear:
-        raise ValueError(f"{who}: give either target or weights / dir_weights, not both")
+        raise ValueError(f"{who}: give either target or weights / dir_weights / transverse weights, not both")
     if target is None and not linear:
-        raise ValueError(f"{who}: give an objective: target, or weights / dir_weights")
+        raise ValueError(f"{who}: give an objective: target, or weights / dir_weights / transverse weights")
     if target is not None and tuple(target.shape) != (nb, 6, 6):
         raise ValueError(f"{who}: target {tuple(target.shape)}, expected [{nb}, 6, 6]")
     if directions is not None and (directions.dim() != 2 or directions.shape[1] != 3):
@@ -425,7 +462,8 @@ def optimize_design(model, batch, *, target: Optional[torch.Tensor] = None, weig
     if linear:
         from .elastic import ELASTIC_COLUMNS
         if weights is None:
-            weights = torch.zeros(nb, len(ELASTIC_COLUMNS), dtype=dir_weights.dtype, device=dir_weights.device)
+            like = next(w for w in (dir_weights, transverse_weights, transverse_dir_weights) if w is not None)
+            weights = torch.zeros(nb, len(ELASTIC_COLUMNS), dtype=like.dtype, device=like.device)
         if tuple(weights.shape) != (nb, len(ELASTIC_COLUMNS)):
             raise ValueError(f"{who}: weights {tuple(weights.shape)}, expected [{nb}, {len(ELASTIC_COLUMNS)}]")
         if dir_weights is not None and (directions is None or tuple(dir_weights.shape) != (nb, int(directions.shape[0]))):
@@ -474,16 +512,20 @@ def optimize_design(model, batch, *, target: Optional[torch.Tensor] = None, weig
             d, j = value(c)
             return {"objective": j}, [c], [d * inv[:, None, None]]
     else:
-        inner = _property_cotangents(weights, directions, dir_weights, who)
+        inner = _property_cotangents(weights, directions, dir_weights, who, transverse_weights=transverse_weights,
+                                     transverse_dir_weights=transverse_dir_weights)
 
         def weighted(w, v):
-            return torch.where(w != 0, w * v, torch.zeros_like(v)).sum(dim=1)
+            return torch.where(w != 0, w * v, torch.zeros_like(v)).flatten(1).sum(dim=1)
 
         def cotangents(c):
             extra, outputs, grads = inner(c)
             j = weighted(grads[0], extra["properties"])
-            if len(outputs) > 1:
-                j = j + weighted(grads[1], extra["e_dir"])
+            rest = list(grads[1:])
+            for given, key in ((dir_weights, "e_dir"), (transverse_weights, "transverse"),
+                               (transverse_dir_weights, "t_dir")):
+                if given is not None:
+                    j = j + weighted(rest.pop(0), extra[key])
             extra["objective"] = j
             return extra, outputs, grads
 

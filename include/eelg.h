@@ -708,6 +708,58 @@ int eelg_elastic_props_bwd(const float* s, const float* dirs, const float* e_dir
                            const float* g_props, const float* g_e_dir, int n_graphs, int n_dirs,
                            float* g_c, void* stream);
 
+/* ---- Shear, Poisson's ratio and compressibility surfaces and their gradient --------------------
+ * (csrc/eelg_transverse.hip; the arithmetic of one matrix and one direction in
+ * csrc/eelg_transverse.h)
+ * c, dirs, A and S = A^-1 (fp64) as above.  For a unit direction d and a unit n orthogonal to d
+ *   G(d, n)  = 1 / (4 S'_1212)        nu(d, n) = -S'_1122 / S'_1111        beta(d) = S_ijkk d_i d_j
+ * with S' the compliance in a frame whose first two axes are d and n.  Both 1 / G and nu are a mean
+ * plus one sinusoid in twice the transverse angle, so their extremes over n are closed forms:
+ *   frame   j = the first index of the smallest |d_j|, t1 = normalize(d x e_j), t2 = d x t1
+ *   M(T)    = (T11, T22, T33, r2 T23, r2 T13, r2 T12),  sym(u (x) v) = (u v^T + v u^T) / 2
+ *   a = m(d), T1 = M(sym(d (x) t1)), T2 = M(sym(d (x) t2)), b1 = m(t1), b2 = m(t2),
+ *   X = M(sym(t1 (x) t2)), u = S a, E = 1 / (a^T u)
+ *   shear   A11 = T1^T S T1, A22 = T2^T S T2, A12 = T1^T S T2
+ *           M_G = 2 (A11 + A22), R_G = 2 hypot(A11 - A22, 2 A12)
+ *           G_lo = 1 / (M_G + R_G), G_hi = 1 / (M_G - R_G)
+ *   Poisson B1 = u^T b1, B2 = u^T b2, Bx = u^T X
+ *           M_nu = (B1 + B2) / 2, R_nu = hypot((B1 - B2) / 2, Bx)
+ *           nu_lo = -E (M_nu + R_nu), nu_hi = -E (M_nu - R_nu)
+ *   beta    = u_1 + u_2 + u_3
+ * t_dir [n_graphs, n_dirs, EELG_TRANSVERSE_DIR_COLS]: 0 G_lo, 1 G_hi, 2 nu_lo, 3 nu_hi, 4 beta.
+ * props [n_graphs, EELG_TRANSVERSE_COLS]:
+ *   0 G_min = min_p G_lo, 1 G_max = max_p G_hi, 2 nu_min = min_p nu_lo, 3 nu_max = max_p nu_hi,
+ *   4 beta_min, 5 beta_max: first extremes of the stored fp32 values (the smaller index wins a tie,
+ *   a NaN never wins; NaN with n_dirs == 0);  6 spd as in eelg_elastic_props.
+ * arg [n_graphs, 6] int32: the direction index of each extreme (-1 where the extreme is NaN).
+ * n_ext [n_graphs, 4, 3]: the transverse unit vector n = cos(th) t1 + sin(th) t2 at which G_min,
+ * G_max, nu_min, nu_max are taken in their direction: 2 th = atan2(2 A12, A11 - A22) resp.
+ * atan2(Bx, (B1 - B2) / 2), plus pi for G_max / nu_max; an amplitude of exactly 0 gives th = 0 resp.
+ * pi / 2.  s [n_graphs, 21] fp64: the packed lower triangle of S (entry (i, j), i >= j, at
+ * i (i + 1) / 2 + j), kept for the backward: the unit vector (p, q) / R of a hypot amplifies the
+ * rounding of S by M / R, so an fp32 copy is not enough.  A graph with spd == 0: spd 0, NaN in every
+ * other entry of props, t_dir, n_ext and s, arg -1.
+ *
+ * eelg_transverse_props_bwd: g_c [n_graphs, 6, 6] (exactly symmetric) = -S G_S S from the
+ * cotangents g_props [n_graphs, EELG_TRANSVERSE_COLS] and g_t_dir [n_graphs, n_dirs,
+ * EELG_TRANSVERSE_DIR_COLS] (NULL: zero) and the forward's s, props (the spd column) and arg.  Every
+ * term of G_S is d(x^T S y) / dS = sym(x y^T); a hypot passes (p dp + q dq) / R and exactly 0 where
+ * R == 0; the cotangent of an extreme goes to the direction arg names, alone.  A graph with spd == 0
+ * gets exactly zero: none of its cotangents is read.
+ *
+ * One wavefront per graph, directions strided over the lanes, fixed xor butterflies; no LDS, scratch
+ * or atomics.  A graph's rows and gradient depend on (its matrix, dirs, n_dirs, its cotangents)
+ * alone: bitwise equal in any batch, at any position, on every run.
+ * n_graphs == 0: nothing is launched, 0 is returned whatever the pointers.  -2: n_graphs < 0,
+ * n_dirs < 0, a null pointer (dirs, t_dir: only with n_dirs > 0), s not aligned to 8 bytes. */
+#define EELG_TRANSVERSE_COLS 7
+#define EELG_TRANSVERSE_DIR_COLS 5
+int eelg_transverse_props(const float* c, const float* dirs, int n_graphs, int n_dirs, float* props,
+                          float* t_dir, int* arg, float* n_ext, double* s, void* stream);
+int eelg_transverse_props_bwd(const double* s, const float* dirs, const float* props, const int* arg,
+                              const float* g_props, const float* g_t_dir, int n_graphs, int n_dirs,
+                              float* g_c, void* stream);
+
 /* ---- The tail of the training step: loss, gradient norm, clip + AdamW --------------------------
  * (csrc/eelg_optim.hip; per-element arithmetic in csrc/eelg_adamw.h)
  *
